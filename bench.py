@@ -19,6 +19,16 @@ cpu_baseline: the CPU oracle (faithful single-thread C restatement of
 SortMergeReaderWithLoserTree + Deduplicate, oracle/merge_oracle.c) timed on
 this box's host cores over a bounded prefix sample of the same workload —
 a reported baseline, not the optimization target.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+figure needs: generate-or-load the seeded data, stage, warm up, time the N
+steps, print the result line. The per-kernel and roofline figures ride on
+the timed steps themselves (HIP events inside the library), so they stay.
+`--full` adds what takes work of its own: today the cpu_baseline leg.
+
+`--dump-outputs DIR` writes, after the clock has stopped, what the last
+timed step handed its caller (see OutputDump) so two builds can be compared
+output for output on the same seeded input.
 """
 
 import argparse
@@ -63,6 +73,120 @@ def pmc_traffic(dom, args):
     return None
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # sampled arrays; the cap on a dump is 64 MB
+DUMP_SEED = 0x5EED
+
+
+class _DevArray:
+    """A device buffer of a batch, described through
+    __cuda_array_interface__ so torch can view it without a copy."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {
+            "shape": (n,), "typestr": typestr, "data": (ptr, False),
+            "version": 2}
+
+
+class OutputDump:
+    """Collects the batches one step yields (device output mode) and writes
+    them as DIR/<name>.npy.
+
+    A step's output is GBs, so each column is written as a fixed, seeded
+    sample of rows (the same rows for every column; their positions in the
+    step's concatenated output are in sample_rows.npy) plus a checksum over
+    ALL rows. Files, all float64 unless noted:
+      <col>.npy          sampled values (the bench schema is integer columns
+                         well inside 2^53, so float64 holds them exactly);
+                         0 where the row's value is null
+      <col>__valid.npy   float32 1/0, only for columns with a validity buffer
+      <col>__sum.npy     [hi32, lo32] of the column's sum over every row of
+                         the step, mod 2^64 (nulls count 0)
+      sample_rows.npy    output row index of each sampled row
+      batch_rows.npy     rows per batch, in order
+    """
+
+    def __init__(self, device):
+        import numpy as np
+        self.np = np
+        self.device = device
+        # batches per step, set by the caller once an earlier step has
+        # shown it; else a guess that write() corrects by thinning the sample
+        self.n_batches = 1
+        self.rng = np.random.default_rng(DUMP_SEED)
+        self.names = []
+        self.parts = {}
+        self.sums = {}
+        self.sample_rows = []
+        self.batch_rows = []
+        self.row0 = 0
+
+    def take(self, b):
+        """Copy the sample and checksums out of one device batch; its
+        buffers are only valid until the plan's next read_next."""
+        import torch
+        from paimon_amd.reader import _DT_NP
+        np = self.np
+        dev = f"cuda:{self.device}"
+        n = int(b.n_rows)
+        n_cols = int(b.n_cols)
+        row_bytes = n_cols * (8 + 4) + 8
+        quota = max(1, DUMP_BUDGET_BYTES // row_bytes // self.n_batches)
+        idx = np.sort(self.rng.choice(n, size=min(n, quota), replace=False))
+        idx_t = torch.as_tensor(idx, device=dev)
+        for c in range(n_cols):
+            col = b.cols[c]
+            name = col.name.decode()
+            if name not in self.parts:
+                self.names.append(name)
+                self.parts[name] = []
+                self.sums[name] = 0
+            if n == 0 or not col.data:
+                continue
+            dt = np.dtype(_DT_NP[col.dtype])
+            t = torch.as_tensor(_DevArray(col.data, n, dt.str), device=dev)
+            valid = None
+            if col.valid:
+                valid = torch.as_tensor(_DevArray(col.valid, n, "|u1"),
+                                        device=dev) != 0
+                t = torch.where(valid, t, torch.zeros_like(t))
+            total = int(t.to(torch.int64).sum())  # wraps mod 2^64
+            self.sums[name] = (self.sums[name] + total) & (2**64 - 1)
+            self.parts[name].append(
+                t[idx_t].to(torch.float64).cpu().numpy())
+            if valid is not None:
+                self.parts.setdefault(name + "__valid", []).append(
+                    valid[idx_t].to(torch.float32).cpu().numpy())
+        self.sample_rows.append(idx + self.row0)
+        self.batch_rows.append(n)
+        self.row0 += n
+
+    def write(self, out_dir):
+        np = self.np
+        os.makedirs(out_dir, exist_ok=True)
+        rows = (np.concatenate(self.sample_rows) if self.sample_rows
+                else np.empty(0, np.int64))
+        keep = None
+        n_arrays = len(self.parts)
+        cap = DUMP_BUDGET_BYTES // (8 * (n_arrays + 1))
+        if len(rows) > cap:  # more batches than take() was told to expect
+            keep = np.sort(self.rng.choice(len(rows), size=cap,
+                                           replace=False))
+            rows = rows[keep]
+        for name, parts in self.parts.items():
+            a = (np.concatenate(parts) if parts
+                 else np.empty(0, np.float64))
+            np.save(os.path.join(out_dir, name + ".npy"),
+                    a if keep is None else a[keep])
+        for name in self.names:
+            s = self.sums[name]
+            np.save(os.path.join(out_dir, name + "__sum.npy"),
+                    np.array([s >> 32, s & 0xFFFFFFFF], np.float64))
+        np.save(os.path.join(out_dir, "sample_rows.npy"),
+                rows.astype(np.float64))
+        np.save(os.path.join(out_dir, "batch_rows.npy"),
+                np.array(self.batch_rows, np.float64))
+
+
 def get_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -80,14 +204,48 @@ def get_args():
                     help="supplementary merge-engine variants; the default "
                     "metric line is deduplicate per BASELINE.json configs[1]")
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--data-dir", default=os.path.join(REPO, "data"))
+    ap.add_argument("--data-dir", default=None,
+                    help="where the generated run files are kept between "
+                    "runs (default: data/ in the repository; if that cannot "
+                    "be written, a cache folder under the home directory, "
+                    "else a temporary folder removed at exit)")
     ap.add_argument("--cpu-baseline-rows", type=int, default=2_000_000,
                     help="prefix rows per run for the CPU-oracle baseline; "
-                    "0 disables")
+                    "0 disables (only measured with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                    "the CPU-oracle baseline (cpu_baseline in the result)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                    "output batches as DIR/<name>.npy (seeded row sample + "
+                    "whole-column checksums, see OutputDump)")
     return ap.parse_args()
 
 
+def default_data_dir():
+    """The first of data/ in the repository and a per-user cache folder
+    that can be created and written; the repository may be a read-only
+    checkout. Failing both, a temporary folder that is removed at exit."""
+    for d in (os.path.join(REPO, "data"),
+              os.path.join(os.path.expanduser("~"), ".cache", "paimon_hip",
+                           "bench_data")):
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    import atexit
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="paimon_hip_bench_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    return d
+
+
 def ensure_data(args, rank):
+    if args.data_dir is None:
+        args.data_dir = default_data_dir()
     from paimon_amd.datagen import (gen_runs_dedup, gen_runs_partial_update,
                                     write_runs)
     pu = args.engine in ("partial-update", "aggregation")
@@ -199,28 +357,49 @@ def main():
                          aggregations=aggs)
     t_stage = time.perf_counter() - t_stage0
 
-    def one_step():
+    def one_step(take=None, expect=None):
+        """One pass; returns (rows, batches, last batch). `take` (the dump,
+        last timed step only) is called on a batch before the read_next that
+        reuses its buffers — except on the step's final batch when `expect`,
+        the batch count of an earlier step, identifies it: that one is
+        returned still resident and copied after the clock has stopped."""
         plan.reset()
-        rows = 0
+        rows = nb = 0
+        b = None
         while True:
-            b = plan.read_next()
-            if b is None:
+            if take is not None and b is not None and nb != expect:
+                take(b)
+                b = None
+            nxt = plan.read_next()
+            if nxt is None:
                 break
+            b = nxt
             rows += b.n_rows
-        return rows
+            nb += 1
+        return rows, nb, b
 
     # warmup
     rows_out = 0
+    n_batches = None
     for _ in range(args.warmup):
-        rows_out = one_step()
+        rows_out, n_batches, _ = one_step()
     stats0 = plan.stats()
+
+    dump = None
+    dump_tail = None
+    if args.dump_outputs and rank == 0:
+        dump = OutputDump(local_rank)
 
     if dist:
         dist.barrier()
     torch.cuda.synchronize(local_rank)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        rows_out = one_step()
+    for i in range(args.steps):
+        if dump is not None and i == args.steps - 1:
+            dump.n_batches = n_batches or 1
+            rows_out, _, dump_tail = one_step(dump.take, n_batches)
+        else:
+            rows_out, n_batches, _ = one_step()
     torch.cuda.synchronize(local_rank)
     if dist:
         dist.barrier()
@@ -336,7 +515,17 @@ def main():
         "gen_seconds": round(t_gen, 2),
     }
 
-    if rank == 0 and n_gpus == 1 and args.cpu_baseline_rows > 0:
+    if dump is not None:
+        if dump_tail is not None:
+            dump.take(dump_tail)
+        if sum(dump.batch_rows) != rows_out:
+            raise RuntimeError(
+                f"--dump-outputs captured {sum(dump.batch_rows)} of the last "
+                f"step's {rows_out} rows (batch count changed between steps)")
+        dump.write(args.dump_outputs)
+
+    if (args.full and rank == 0 and n_gpus == 1
+            and args.cpu_baseline_rows > 0):
         result["cpu_baseline"] = cpu_baseline(args, out_dir)
 
     plan.close()

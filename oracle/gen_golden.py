@@ -111,6 +111,35 @@ def main():
     np.savez_compressed(os.path.join(GOLDEN_DIR, "first_row_5x1200.npz"), **d)
     print("first-row golden:", len(out), "records")
 
+    gen_random_dedup()
+
+
+def gen_random_dedup():
+    # Case E: the randomized small-run sweep of
+    # tests/test_oracle_merge.py::TestLiveVsPypaimon — 10 seeded trials of
+    # 1-6 ragged runs, inputs and pypaimon's merged (key, seq) both ways of
+    # drop-delete, so the test needs no live pypaimon
+    from tests.util import random_runs
+    rng = np.random.default_rng(99)
+    d = {"n_trials": np.array(10)}
+    n_out = 0
+    for t in range(10):
+        runs = random_runs(rng, int(rng.integers(1, 7)), 60, 90,
+                           n_value_cols=2)
+        _save_runs(d, f"t{t}_in", runs)
+        for dd in (True, False):
+            out = merge_with_pypaimon(runs, "deduplicate", drop_delete=dd)
+            d[f"t{t}_dd{int(dd)}_key"] = np.array([o[0] for o in out],
+                                                  np.int64)
+            d[f"t{t}_dd{int(dd)}_seq"] = np.array([o[1] for o in out],
+                                                  np.int64)
+            n_out += len(out)
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "dedup_random_10.npz"), **d)
+    print("random dedup golden:", n_out, "records over 10 trials")
+
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["random"]:
+        gen_random_dedup()
+    else:
+        main()

@@ -1,8 +1,8 @@
 """Drive pypaimon — the reference's own Python implementation — as a parity
 pin for the oracle. CONTAINER-ONLY: requires /root/reference to exist; never
-imported by -m gpu tests, smoke() or bench.py. Used by
-tests gated on the reference being present and by gen_golden.py to produce
-the committed fixtures under tests/golden/.
+imported by the tests, smoke() or bench.py. Used by
+gen_golden.py and scripts/pypaimon_baseline.py only; the tests read what
+gen_golden.py recorded under tests/golden/.
 
 pypaimon imports after stubbing 4 pure-Python deps absent from this image
 (cachetools, readerwriterlock, polars, fastavro — import-only stubs).

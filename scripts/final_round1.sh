@@ -7,7 +7,8 @@ mkdir -p gpurun_out/prof
 python3 -m pytest tests -m gpu -q 2>&1 | tail -2
 python3 -c "import __graft_entry__ as g; g.smoke()"
 # default metric line (BASELINE.json configs[1]) with CPU baseline
-python3 bench.py --steps 10 --warmup 3 > gpurun_out/bench_r01_final.json \
+FINAL_JSON=$PWD/profiles/bench_r01_final.json  # where it is committed
+python3 bench.py --full --steps 10 --warmup 3 > "$FINAL_JSON" \
     2> gpurun_out/bench_r01_final.err
 echo BENCH_RC=$?
 # supplementary engine lines
@@ -69,4 +70,4 @@ rm -f /root/repo/gpurun_out/tprof/*counter*.csv
 rm -f /root/repo/gpurun_out/prof/*counter_collection*.csv \
       /root/repo/gpurun_out/prof/*kernel_trace*.csv
 ls /root/repo/gpurun_out/prof/ | head
-tail -c 600 /root/repo/gpurun_out/bench_r01_final.json
+tail -c 600 "$FINAL_JSON"

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/prof gpurun_out/tprof
 timeout 700 python3 -m pytest tests -m gpu -q 2>&1 | tail -2
 python3 -c "import __graft_entry__ as g; g.smoke()" && echo SMOKE_OK
 # default metric line (BASELINE.json configs[1]) with CPU baselines
-timeout 300 python3 bench.py --steps 10 --warmup 3 \
+timeout 300 python3 bench.py --full --steps 10 --warmup 3 \
     > gpurun_out/bench_r02_final.json 2> gpurun_out/bench_r02_final.err
 echo BENCH_RC=$?
 # compressed-table variant (reference default file.compression = zstd;
