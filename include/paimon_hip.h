@@ -104,6 +104,8 @@ typedef struct pmh_stats {
     int64_t path_mode;       /* 0 = 3-kernel chain, 1 = fused in-kernel
                               * emission, 2 = fused + split value emission */
     int64_t gpu_zstd_pages;  /* pages decompressed by k_zstd_pages */
+    double lookup_ms;        /* device time in k_lookup_probe (lookup
+                              * changelog producer; not part of merge_ms) */
 } pmh_stats;
 
 /* Session: owns the device + stream pool. device < 0 opens a host-only
@@ -121,7 +123,26 @@ void pmh_close_session(pmh_session_t *s);
  *   "output": "device" | "host",
  *   "files": [{"path": "...", "rowCount": N, "minKey": x, "maxKey": y,
  *              "level": L}, ...]                              // DataFileMeta
+ *   // optional changelog stream (served by pmh_changelog_next):
+ *   "changelog_producer": "none" | "full-compaction" | "lookup",
+ *   "changelog_row_deduplicate": false,
+ *   "max_level": N,              // full-compaction only (num-levels - 1)
+ *   "lookup_files": [...]        // lookup only; same shape as "files"
  * }
+ * changelog_producer = "lookup" (LookupChangelogMergeFunctionWrapper.java:
+ * 104-163 over LookupMergeFunction.java:66-135, deduplicate engine): "files"
+ * are the compaction's inputs (level 0 plus any upper-level members) and
+ * "lookup_files" the data files of the levels ABOVE the compaction's output
+ * level (outputLevel+1 .. maxLevel, LookupMergeTreeCompactRewriter.java:
+ * 211-219). They group by level into one sorted run per level, are staged
+ * once and stay device-resident across sections and pmh_plan_reset; a key
+ * group without an upper-level member is looked up in them, lowest level
+ * first (LookupUtils.java:35-57). Absent/empty lookup_files = empty upper
+ * tree. Limits (plan creation fails otherwise): runs of a section + lookup
+ * levels <= 32; each lookup level < 2^27 rows; every lookup level above
+ * every level in "files"; files of one lookup level key-disjoint;
+ * deduplicate engine only; a single integer key column; no ignore_delete,
+ * no sequence fields, no PMH_FUSED=1, no deletionVector on a lookup file.
  * Staging (file read + H2D of encoded column chunks + page tables) happens
  * here; pmh_read_next launches only device work. */
 pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json);
@@ -139,8 +160,10 @@ int pmh_plan_close(pmh_plan_t *p);
  * "full-compaction" in the plan JSON, with "max_level" and optional
  * "changelog_row_deduplicate"): the FullChangelogMergeFunctionWrapper
  * stream (INSERT / UPDATE_BEFORE / UPDATE_AFTER / DELETE rows in key
- * order, same schema as the main batch). Valid until the next read_next.
- * Returns row count or < 0. */
+ * order, same schema as the main batch). changelog_producer = "lookup"
+ * serves the LookupChangelogMergeFunctionWrapper stream the same way; a row
+ * built from a looked-up record carries that record's key, sequence number
+ * and values. Valid until the next read_next. Returns row count or < 0. */
 int64_t pmh_changelog_next(pmh_plan_t *plan, pmh_batch *out);
 
 int pmh_plan_reset(pmh_plan_t *p);
@@ -203,6 +226,17 @@ int64_t pmh_debug_zstd_enc_gpu(const void *src, int64_t n, void *dst,
  * entry pinning the parser against independently-serialized fixtures. */
 int64_t pmh_debug_parse_dv(const char *path, int64_t offset, int64_t length,
                            int64_t *out, int64_t cap);
+
+/* Point lookup into sorted levels on the host, through the same search core
+ * k_lookup_probe runs on the device (lookup_core.h): level_keys[l] holds
+ * level_rows[l] ascending unique int64 keys. Per query, out_level gets the
+ * index of the FIRST level holding the key (levels are searched in array
+ * order, LookupUtils.java:35-57) and out_row the row inside it; both -1
+ * when no level holds it. Returns 0, or -1 with pmh_last_error() set. */
+int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
+                           const int64_t *level_rows, const int64_t *queries,
+                           int64_t n_queries, int32_t *out_level,
+                           int64_t *out_row);
 
 /* Restatement of IntervalPartition.partition() for int64 keys
  * (mergetree/compact/IntervalPartition.java:67-125): given n files'

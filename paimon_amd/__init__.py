@@ -9,6 +9,7 @@ from .reader import (  # noqa: F401
     load_lib,
     debug_footer,
     interval_partition,
+    debug_lookup_probe,
     file_descs_from_metas,
     write_parquet,
     LIB_PATH,

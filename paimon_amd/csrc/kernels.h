@@ -216,7 +216,24 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
                                   uint16_t *group_start, uint32_t *err_flag,
                                   const uint8_t *run_levels, int max_level,
                                   uint64_t *cl_entries, int32_t *cl_counts,
+                                  const uint32_t *probe_words,
+                                  const int64_t *probe_off,
                                   hipStream_t stream);
+
+// lookup changelog producer (LookupChangelogMergeFunctionWrapper): merge
+// flags bit selecting the lookup walk of k_merge_tiles. keys/seqs/kinds/
+// run_levels then hold k + n_levels slots (the lookup levels after the k
+// merge runs) and probe_words/probe_off come from pmh_launch_lookup_probe.
+constexpr int PMH_FLAG_LOOKUP = 1 << 15;
+
+// k_lookup_probe: for every row of the section's level-0 runs (probe_off[r]
+// >= 0: word offset of run r's first row; < 0: run r is not probed), the
+// packed (slot, row) of the first lookup level — slots k .. k+n_levels-1,
+// lowest level first — that holds the row's key, or 0xFFFFFFFF.
+hipError_t pmh_launch_lookup_probe(const DevCol *keys, const int64_t *lens,
+                                   const int64_t *probe_off, int k,
+                                   int n_levels, int64_t max_run_rows,
+                                   uint32_t *words, hipStream_t stream);
 
 hipError_t pmh_launch_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
                                  int64_t *tile_offsets, int64_t *total_out,

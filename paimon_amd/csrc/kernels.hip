@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "lookup_core.h"
 #include "zstd_core.h"
 
 #define DEV __device__ __forceinline__
@@ -390,7 +391,13 @@ DEV bool ps2m_isadd(int64_t w) { return w & 1; }
 // PartialUpdateMergeFunction.java:170-186) — retracts set err_flag.
 // Separate template instantiations keep the PU path's extra registers out
 // of the deduplicate kernel.
-template <bool PU, bool FR>
+//
+// LK=true: lookup changelog producer (flags bit PMH_FLAG_LOOKUP; bits 8..14
+// are the profiling knobs) — the winner walk
+// applies LookupMergeFunction's level rules and reads k_lookup_probe's
+// per-row probe words; its own instantiation, so the other modes' code is
+// untouched.
+template <bool PU, bool FR, bool LK = false>
 __launch_bounds__(PMH_TILE_THREADS) __global__
 void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                    const int64_t *lens, int k, const int32_t *cuts,
@@ -403,7 +410,12 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                    // per-group provisional changelog entries (2 slots per
                    // group; k_cl_finalize compacts them to rows)
                    const uint8_t *run_levels, int max_level,
-                   uint64_t *cl_entries, int32_t *cl_counts) {
+                   uint64_t *cl_entries, int32_t *cl_counts,
+                   // lookup changelog (LK): one word per row of the level-0
+                   // runs (k_lookup_probe), run r's rows at probe_off[r];
+                   // keys/seqs/kinds then carry the lookup-level slots
+                   // after the k merge runs
+                   const uint32_t *probe_words, const int64_t *probe_off) {
     const bool drop_delete = flags & 1;
     const bool ignore_delete = flags & 2;
     // FR = first-row engine (FirstRowMergeFunction.java:32-77): keep the
@@ -777,6 +789,121 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             int32_t nloc = 0, ncl = 0;
             for (int32_t i = my_lo; i < my_hi; i++) {
                 if (!sm.head[i]) continue;
+                if constexpr (LK) {
+                    // lookup changelog (LookupChangelogMergeFunctionWrapper
+                    // .java:104-163 over LookupMergeFunction.java:66-135):
+                    // the merge sees the level-0 members plus `high`, the
+                    // member of the lowest level > 0 (other upper members
+                    // are dropped); without such a member `high` is the
+                    // probe hit in the lookup levels, if any.
+                    uint16_t s_lo = 0, s_l0 = 0, s_hi = 0;
+                    int64_t v_lo = 0, v_hi = 0;
+                    int lv_hi = 0;
+                    bool has_lo = false, has_hi = false;
+                    for (int32_t x = i;; x++) {
+                        const uint16_t sx = mo[x];
+                        const int64_t v = sm.sseq[sx];
+                        if (v != PMH_DEAD) {
+                            int r = 0;
+                            while (r + 1 <= k - 1 &&
+                                   sm.segoff[r + 1] <= (int32_t)sx)
+                                r++;
+                            const int lv = run_levels[r];
+                            if (lv > 0) {
+                                // pickHighLevel: lowest level; a level tie
+                                // goes to the earlier record in merge order
+                                if (!has_hi || lv < lv_hi ||
+                                    (lv == lv_hi && v < v_hi)) {
+                                    s_hi = sx;
+                                    v_hi = v;
+                                    lv_hi = lv;
+                                    has_hi = true;
+                                }
+                            } else {
+                                if (!has_lo) s_l0 = sx;
+                                if (!has_lo || v > v_lo) {
+                                    s_lo = sx;
+                                    v_lo = v;
+                                }
+                                has_lo = true;  // containLevel0
+                            }
+                        }
+                        if (!(x + 1 < M && !sm.head[x + 1])) break;
+                    }
+                    if (!has_lo && !has_hi) continue;  // no live member
+                    uint32_t loc_hi = 0;
+                    int64_t w_hi = 0;
+                    bool hh = has_hi, hit = false;
+                    if (has_hi) {
+                        loc_hi = (uint32_t)packm(s_hi);
+                        w_hi = v_hi;
+                    } else {
+                        const uint32_t pm = (uint32_t)packm(s_l0);
+                        const uint32_t w =
+                            probe_words[probe_off[pm >> PMH_ROW_BITS] +
+                                        (int64_t)(pm & PMH_ROW_MASK)];
+                        if (w != PLK_MISS) {
+                            // a record of ANY kind counts (a DELETE too)
+                            const int slot = w >> PMH_ROW_BITS;
+                            const int64_t row = w & PMH_ROW_MASK;
+                            const int64_t sq = reinterpret_cast<const int64_t *>(
+                                seqs[slot].addr0)[row];
+                            const int32_t kd = reinterpret_cast<const int32_t *>(
+                                kinds[slot].addr0)[row];
+                            w_hi = (sq << 1) | (int64_t)(kd == 0 || kd == 2);
+                            loc_hi = w;
+                            hh = hit = true;
+                        }
+                    }
+                    // deduplicate result = last candidate. A member `high`
+                    // sorts by (seq, isAdd); a looked-up one is inserted
+                    // before the first candidate with a strictly greater
+                    // sequence number (KeyValueBuffer.insertInto), so it
+                    // wins exactly when its seq >= every member's.
+                    const bool take_hi =
+                        hh && (!has_lo || (hit ? (w_hi >> 1) >= (v_lo >> 1)
+                                               : w_hi >= v_lo));
+                    const uint32_t loc_res =
+                        take_hi ? loc_hi : (uint32_t)packm(s_lo);
+                    const int64_t w_res = take_hi ? w_hi : v_lo;
+                    if (has_lo) {
+                        // setChangelog(before = high, after = result),
+                        // independent of drop-delete
+                        const bool b_add = hh && (w_hi & 1);
+                        const bool a_add = w_res & 1;
+                        auto mkl = [&](uint32_t loc, uint64_t kd,
+                                       bool pd) -> uint64_t {
+                            return (uint64_t)loc | (kd << 32) | (1ull << 35) |
+                                   (pd ? (1ull << 36) : 0);
+                        };
+                        uint64_t e0 = 0, e1 = 0;
+                        int cl_n = 0;
+                        if (!b_add) {
+                            if (a_add) {  // INSERT(after)
+                                e0 = mkl(loc_res, 0, false);
+                                cl_n = 1;
+                            }
+                        } else if (!a_add) {  // DELETE(before)
+                            e0 = mkl(loc_hi, 3, false);
+                            cl_n = 1;
+                        } else {  // UPDATE_BEFORE(before), UPDATE_AFTER(after)
+                            e0 = mkl(loc_hi, 1, cl_pend);
+                            e1 = mkl(loc_res, 2, cl_pend);
+                            cl_n = 2;
+                        }
+                        if (cl_n) {
+                            if (pass == 1) {
+                                clout[2 * (my_cl + ncl)] = e0;
+                                clout[2 * (my_cl + ncl) + 1] = e1;
+                            }
+                            ncl++;
+                        }
+                    }
+                    if (drop_delete && !(w_res & 1)) continue;
+                    if (pass == 1) wout[my_off + nloc] = loc_res;
+                    nloc++;
+                    continue;
+                }
                 // walk the group's LIVE members (deletion-vector tombstones
                 // stage as PMH_DEAD), tracking the winner by (elig, sseq):
                 // deduplicate keeps the LAST record, first-row the FIRST
@@ -3227,6 +3354,56 @@ __global__ void k_filter(const DevCol *cols, int n_cols,
     }
 }
 
+// ----------------------------------------------------------- k_lookup_probe
+//
+// Point lookup of the lookup changelog producer (LookupLevels.lookup; the
+// reference probes one key at a time through a local file cache): a batched
+// sorted-probe search over the device-resident lookup levels. Probe keys
+// are the rows of one level-0 run, so they arrive sorted; a workgroup takes
+// PLK_CHUNK consecutive keys, ONE wave bounds the chunk's window in every
+// level from the chunk's first and last key (lane l serves level l — whole-
+// level bisections, once per chunk), and each thread then bisects only
+// inside those windows (lookup_core.h), so the per-key probes touch a small
+// slice of each level that stays cache-resident. Output words are coalesced
+// 4-byte stores. grid = (chunks, k): blockIdx.y is the run.
+__launch_bounds__(256) __global__
+void k_lookup_probe(const DevCol *keys, const int64_t *lens,
+                    const int64_t *probe_off, int k, int n_levels,
+                    uint32_t *words) {
+    __shared__ PlkLevel s_lv[PMH_MAX_RUNS];
+    __shared__ int64_t s_wlo[PMH_MAX_RUNS], s_whi[PMH_MAX_RUNS];
+    const int r = blockIdx.y;
+    const int64_t off = probe_off[r];
+    if (off < 0) return;  // block-uniform: run r is not a level-0 run
+    const int64_t n = lens[r];
+    const int tid = threadIdx.x;
+    if (tid < n_levels) {
+        const DevCol &dc = keys[k + tid];
+        s_lv[tid] = PlkLevel{dc.addr0, lens[k + tid], dc.esize, 0};
+    }
+    const uint64_t kaddr = keys[r].addr0;
+    const int kes = keys[r].esize;
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * PLK_CHUNK; base < n;
+         base += (int64_t)gridDim.x * PLK_CHUNK) {
+        const int cnt = (int)(n - base < PLK_CHUNK ? n - base : PLK_CHUNK);
+        if (tid < n_levels)
+            plk_window(s_lv[tid], plk_key_at(kaddr, base, kes),
+                       plk_key_at(kaddr, base + cnt - 1, kes), &s_wlo[tid],
+                       &s_whi[tid]);
+        __syncthreads();
+        for (int i = tid; i < cnt; i += blockDim.x) {
+            int64_t row = 0;
+            const int l = plk_probe(s_lv, n_levels, s_wlo, s_whi,
+                                    plk_key_at(kaddr, base + i, kes), &row);
+            words[off + base + i] =
+                l < 0 ? PLK_MISS
+                      : ((uint32_t)(k + l) << PMH_ROW_BITS) | (uint32_t)row;
+        }
+        __syncthreads();  // windows are rewritten by the next chunk
+    }
+}
+
 // ------------------------------------------------------------ k_cl_finalize
 //
 // Compact the provisional changelog entries into dense per-tile rows.
@@ -3889,17 +4066,22 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
                                   uint16_t *group_start, uint32_t *err_flag,
                                   const uint8_t *run_levels, int max_level,
                                   uint64_t *cl_entries, int32_t *cl_counts,
+                                  const uint32_t *probe_words,
+                                  const int64_t *probe_off,
                                   hipStream_t stream) {
     int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
-    const bool pu = flags & 4, fr = flags & 8;
+    const bool pu = flags & 4, fr = flags & 8,
+               lk = flags & PMH_FLAG_LOOKUP;
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(PMH_TILE_THREADS), 0,
                            stream, keys, seqs, kinds, lens, k, cuts, n_tiles,
                            tile_rows, flags, tombs, winners, tile_counts,
                            group_start, err_flag, run_levels, max_level,
-                           cl_entries, cl_counts);
+                           cl_entries, cl_counts, probe_words, probe_off);
     };
-    if (pu)
+    if (lk)
+        launch(k_merge_tiles<false, false, true>);  // deduplicate only
+    else if (pu)
         launch(k_merge_tiles<true, false>);  // PU/agg never first-row
     else if (fr)
         launch(k_merge_tiles<false, true>);
@@ -4105,6 +4287,18 @@ hipError_t pmh_launch_filter(const DevCol *cols, int n_cols,
     int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
     hipLaunchKernelGGL(k_filter, dim3(blocks), dim3(256), 0, stream, cols,
                        n_cols, terms, n_terms, rows, tomb);
+    return hipGetLastError();
+}
+
+hipError_t pmh_launch_lookup_probe(const DevCol *keys, const int64_t *lens,
+                                   const int64_t *probe_off, int k,
+                                   int n_levels, int64_t max_run_rows,
+                                   uint32_t *words, hipStream_t stream) {
+    if (k <= 0 || max_run_rows <= 0) return hipSuccess;
+    int64_t chunks = (max_run_rows + PLK_CHUNK - 1) / PLK_CHUNK;
+    int gx = chunks < 2048 ? (int)chunks : 2048;
+    hipLaunchKernelGGL(k_lookup_probe, dim3(gx, k), dim3(256), 0, stream,
+                       keys, lens, probe_off, k, n_levels, words);
     return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 #include "common.h"
 #include "json.h"
 #include "kernels.h"
+#include "lookup_core.h"
 #include "orc_meta.h"
 #include "parquet_meta.h"
 #include "parquet_write.h"
@@ -624,6 +625,13 @@ struct Section {
     int32_t *cl_counts = nullptr;
     int64_t *cl_offsets = nullptr;
     int64_t *cl_total_dev = nullptr;
+    // lookup changelog: the descriptor tables carry n_lookup extra slots
+    // (the plan's lookup levels) after the k merge runs; k_lookup_probe
+    // writes one word per row of the level-0 runs
+    int n_lookup = 0;
+    int64_t *probe_off = nullptr;    // [k] word offset per run, -1 = no probe
+    uint32_t *probe_words = nullptr;
+    int64_t probe_max_rows = 0;      // longest probed run
     std::vector<int64_t *> ckeys;  // per-run composite keys (k_composite)
     // batched decode work (all run-columns in ONE launch each)
     Rlev2Chunk *rlev2_all = nullptr;
@@ -692,6 +700,12 @@ struct pmh_plan_t {
     bool changelog = false;
     bool cl_row_dedup = false;
     int max_level = 0;
+    // changelog-producer = lookup (LookupChangelogMergeFunctionWrapper):
+    // the levels above the compaction's output level, one sorted run per
+    // level (ascending), staged once and resident for the plan's lifetime;
+    // lookup_sec only carries their runs and decode tables
+    bool lookup = false;
+    pmh::Section lookup_sec;
     int64_t cl_rows_last = 0;
     std::vector<void *> out_dev2;
     void **out_ptrs2_dev = nullptr;
@@ -2875,18 +2889,27 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
     return true;
 }
 
+static bool build_decode_tables(pmh_plan_t *plan, Section &sec);
+
 static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
     int k = (int)sec.runs.size();
     int n_cols = (int)plan->cols.size();
-    std::vector<DevCol> keyv(k), seqv(k), kindv(k), allv(k * n_cols);
-    std::vector<int64_t> lens(k);
+    // lookup changelog: every lookup level takes one more slot after the k
+    // merge runs in the key/seq/kind/all-column/level tables, so a packed
+    // (run, row) word can address a lookup-level record; the slots take no
+    // part in partition or merge
+    std::vector<Run> &lk_runs = plan->lookup_sec.runs;
+    const int kt = k + (plan->lookup ? (int)lk_runs.size() : 0);
+    sec.n_lookup = kt - k;
+    std::vector<DevCol> keyv(kt), seqv(kt), kindv(kt), allv(kt * n_cols);
+    std::vector<int64_t> lens(kt);
     int seq_idx = plan->n_key_cols;
     int kind_idx = plan->n_key_cols + 1;
     if (plan->composite_key) sec.ckeys.assign(k, nullptr);
-    for (int r = 0; r < k; r++) {
-        Run &run = sec.runs[r];
+    for (int r = 0; r < kt; r++) {
+        Run &run = r < k ? sec.runs[r] : lk_runs[r - k];
         lens[r] = run.length;
-        sec.total_rows += run.length;
+        if (r < k) sec.total_rows += run.length;
         for (int c = 0; c < n_cols; c++) {
             DevCol dc{(uint64_t)run.cols[c].contig,
                       (uint64_t)run.cols[c].valid_dev,
@@ -2913,11 +2936,11 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
         if (d && host) (void)hipMemcpy(d, host, n, hipMemcpyHostToDevice);
         return d;
     };
-    sec.key_cols = (DevCol *)up(keyv.data(), k * sizeof(DevCol));
-    sec.seq_cols = (DevCol *)up(seqv.data(), k * sizeof(DevCol));
-    sec.kind_cols = (DevCol *)up(kindv.data(), k * sizeof(DevCol));
+    sec.key_cols = (DevCol *)up(keyv.data(), kt * sizeof(DevCol));
+    sec.seq_cols = (DevCol *)up(seqv.data(), kt * sizeof(DevCol));
+    sec.kind_cols = (DevCol *)up(kindv.data(), kt * sizeof(DevCol));
     sec.all_cols = (DevCol *)up(allv.data(), allv.size() * sizeof(DevCol));
-    sec.lens_dev = (int64_t *)up(lens.data(), k * sizeof(int64_t));
+    sec.lens_dev = (int64_t *)up(lens.data(), kt * sizeof(int64_t));
     sec.cuts = (int32_t *)plan->bufs.alloc((sec.n_tiles + 1) * k * 4);
     if (plan->fused) {
         // single-pass path: no winners round-trip, no scan arrays — just
@@ -2939,10 +2962,10 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
             return false;
     }
     if (plan->changelog) {
-        std::vector<uint8_t> lv(k);
-        for (int r = 0; r < k; r++)
-            lv[r] = (uint8_t)sec.runs[r].level;
-        sec.run_levels = (uint8_t *)up(lv.data(), k);
+        std::vector<uint8_t> lv(kt);
+        for (int r = 0; r < kt; r++)
+            lv[r] = (uint8_t)(r < k ? sec.runs[r] : lk_runs[r - k]).level;
+        sec.run_levels = (uint8_t *)up(lv.data(), kt);
         int64_t slots2 = sec.n_tiles * 2 * (PMH_TILE_ROWS + PMH_MAX_RUNS);
         sec.cl_entries = (uint64_t *)plan->bufs.alloc(slots2 * 8);
         sec.cl_rows = (uint64_t *)plan->bufs.alloc(slots2 * 8);
@@ -2952,6 +2975,21 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
         if (!sec.run_levels || !sec.cl_entries || !sec.cl_rows ||
             !sec.cl_counts || !sec.cl_offsets || !sec.cl_total_dev)
             return false;
+    }
+    if (plan->lookup) {
+        // probe words: one per row of the section's level-0 runs
+        std::vector<int64_t> po(k, -1);
+        int64_t words = 0;
+        for (int r = 0; r < k; r++) {
+            if (sec.runs[r].level != 0) continue;
+            po[r] = words;
+            words += sec.runs[r].length;
+            sec.probe_max_rows =
+                std::max(sec.probe_max_rows, sec.runs[r].length);
+        }
+        sec.probe_off = (int64_t *)up(po.data(), k * sizeof(int64_t));
+        sec.probe_words = (uint32_t *)plan->bufs.alloc(words * 4);
+        if (!sec.probe_off || !sec.probe_words) return false;
     }
     sec.total_dev = (int64_t *)plan->bufs.alloc(8);
     sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
@@ -2987,6 +3025,20 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
             if (!sec.row_masks_dev) return false;
         }
     }
+    if (!build_decode_tables(plan, sec)) return false;
+    return sec.key_cols && sec.seq_cols && sec.kind_cols && sec.all_cols &&
+           sec.lens_dev && sec.cuts && sec.total_dev && sec.err_dev;
+}
+
+// Batched read-time decode work of a section's runs (one launch each
+// across every run-column): also serves the plan's lookup levels, which
+// decode once at plan creation.
+static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
+    auto up = [&](const void *host, size_t n) -> void * {
+        void *d = plan->bufs.alloc(n);
+        if (d && host) (void)hipMemcpy(d, host, n, hipMemcpyHostToDevice);
+        return d;
+    };
     std::vector<Rlev2Chunk> all_v;
     std::vector<RleChunk> all_d;
     std::vector<DeltaChunk> all_dc;
@@ -3035,8 +3087,82 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
             !sec.delta_bases)
             return false;
     }
-    return sec.key_cols && sec.seq_cols && sec.kind_cols && sec.all_cols &&
-           sec.lens_dev && sec.cuts && sec.total_dev && sec.err_dev;
+    return true;
+}
+
+// Read-time decode of a section's runs: batched RLEv2/byte-RLE +
+// PRESENT/def-level scatter, plus parquet dictionary materialization per
+// chunk. On failure *what names the failing stage.
+static hipError_t launch_section_decode(pmh_plan_t *p, Section &sec,
+                                        hipStream_t st, const char **what) {
+    if (sec.any_decode) {
+        if (sec.n_rlev2) {
+            hipError_t e = pmh_launch_rlev2(sec.rlev2_all, sec.n_rlev2, st);
+            if (e != hipSuccess) {
+                *what = "rlev2";
+                return e;
+            }
+        }
+        if (sec.n_delta) {
+            hipError_t e = pmh_launch_delta_sum(sec.delta_all, sec.n_delta,
+                                                sec.delta_sums, st);
+            if (e == hipSuccess)
+                e = pmh_launch_delta_scan(sec.dstreams_all, sec.n_dstreams,
+                                          sec.delta_sums, sec.delta_bases,
+                                          st);
+            if (e == hipSuccess)
+                e = pmh_launch_delta_emit(sec.delta_all, sec.n_delta,
+                                          sec.delta_bases, st);
+            if (e != hipSuccess) {
+                *what = "delta";
+                return e;
+            }
+        }
+        for (auto &run : sec.runs) {
+            for (size_t c = 0; c < run.cols.size(); c++) {
+                RunCol &rc = run.cols[c];
+                int es = p->cols[c].stored_esize;
+                if (!rc.dict_encoded && rc.gathers.empty()) continue;
+                if (rc.dict_encoded) {
+                    hipError_t e = pmh_launch_rle_decode(
+                        rc.rle_dev, (int64_t)rc.rle_host.size(), rc.ids_dev,
+                        st);
+                    if (e != hipSuccess) {
+                        *what = "rle_decode";
+                        return e;
+                    }
+                }
+                for (const GatherTask &gt : rc.gathers) {
+                    if (!gt.n) continue;
+                    uint8_t *dst = gt.to_dense
+                                       ? (uint8_t *)rc.dense_dev
+                                       : (uint8_t *)rc.contig;
+                    // in_place: ORC dictionary-string LOCAL ids were
+                    // RLEv2-decoded at the target already; remap to global
+                    const int32_t *ids =
+                        gt.in_place
+                            ? (const int32_t *)(dst + gt.start * es)
+                            : rc.ids_dev + gt.start;
+                    hipError_t e = pmh_launch_dict_gather(
+                        ids, gt.dict_dev, gt.n, dst + gt.start * es, es,
+                        st);
+                    if (e != hipSuccess) {
+                        *what = "dict_gather";
+                        return e;
+                    }
+                }
+            }
+        }
+        if (sec.n_def) {
+            hipError_t e =
+                pmh_launch_level_scatter(sec.def_all, sec.n_def, st);
+            if (e != hipSuccess) {
+                *what = "level_scatter";
+                return e;
+            }
+        }
+    }
+    return hipSuccess;
 }
 
 }  // namespace pmh
@@ -3318,10 +3444,34 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                               "later round)");
                     return nullptr;
                 }
+            } else if (cp == "lookup") {
+                // LookupChangelogMergeFunctionWrapper: changelog at every
+                // level-0 compaction; the upper levels come as lookup_files
+                plan->changelog = true;
+                plan->lookup = true;
+                plan->cl_row_dedup =
+                    j["changelog_row_deduplicate"].as_bool(false);
+                if (engine != "deduplicate") {
+                    set_error("changelog_producer=lookup is supported for "
+                              "the deduplicate engine in v1 (first-row uses "
+                              "FirstRowMergeFunctionWrapper; partial-update/"
+                              "aggregation changelog is a later round)");
+                    return nullptr;
+                }
+                if (plan->ignore_delete) {
+                    set_error("changelog_producer=lookup cannot be combined "
+                              "with ignore_delete in v1");
+                    return nullptr;
+                }
+                if (plan->composite_key) {
+                    set_error("changelog_producer=lookup needs a single "
+                              "integer key column in v1 (composite keys are "
+                              "a later round)");
+                    return nullptr;
+                }
             } else if (cp != "none") {
                 set_error("changelog_producer '%s' not supported (none | "
-                          "full-compaction; lookup changelog is a later "
-                          "round)", cp.c_str());
+                          "full-compaction | lookup)", cp.c_str());
                 return nullptr;
             }
         }
@@ -3338,9 +3488,10 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             plan->fused = !plan->pu && want_fused;
             if (plan->changelog && plan->fused) {
                 if (plan->n_useq > 0 || (pf && pf[0] != '0')) {
-                    set_error("changelog_producer=full-compaction runs on "
+                    set_error("changelog_producer=%s runs on "
                               "the classic merge chain (no sequence.field / "
-                              "PMH_FUSED=1 combination in v1)");
+                              "PMH_FUSED=1 combination in v1)",
+                              plan->lookup ? "lookup" : "full-compaction");
                     return nullptr;
                 }
                 plan->fused = false;
@@ -3465,6 +3616,92 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
 
         auto sections = interval_partition(files, plan->changelog);
         auto t0 = std::chrono::steady_clock::now();
+        if (plan->lookup) {
+            // lookup levels (LookupMergeTreeCompactRewriter.java:211-219:
+            // the lookup starts at outputLevel + 1): group lookup_files by
+            // level into one sorted run per level, files of a level
+            // concatenated in key order — staged ONCE here, before the
+            // sections, whose descriptor tables reference them
+            std::map<int, std::vector<FileDesc>> by_level;
+            int max_merge_level = 0;
+            for (const auto &fd : files)
+                max_merge_level = std::max(max_merge_level, fd.level);
+            for (const auto &fj : j["lookup_files"].arr) {
+                FileDesc fd;
+                fd.path = fj["path"].as_str();
+                fd.row_count = fj["rowCount"].as_i64();
+                fd.min_key = fj["minKey"].as_i64();
+                fd.max_key = fj["maxKey"].as_i64();
+                fd.level = (int)fj["level"].as_i64();
+                if (!fj["deletionVector"].obj.empty()) {
+                    set_error("lookup file %s carries a deletionVector: the "
+                              "deletion-vector lookup strategy is not "
+                              "supported in v1", fd.path.c_str());
+                    return nullptr;
+                }
+                if (fd.level <= max_merge_level || fd.level > 255) {
+                    set_error("lookup file %s: level %d must be above every "
+                              "level in files (max %d) — lookup levels are "
+                              "outputLevel+1 .. maxLevel", fd.path.c_str(),
+                              fd.level, max_merge_level);
+                    return nullptr;
+                }
+                by_level[fd.level].push_back(fd);
+            }
+            size_t max_k = 0;
+            for (auto &sf : sections) max_k = std::max(max_k, sf.size());
+            if (max_k + by_level.size() > (size_t)PMH_MAX_RUNS) {
+                set_error("%zu merge runs + %zu lookup levels exceed the %d "
+                          "run slots of a section", max_k, by_level.size(),
+                          PMH_MAX_RUNS);
+                return nullptr;
+            }
+            for (auto &kv : by_level) {
+                auto &lf = kv.second;
+                std::sort(lf.begin(), lf.end(),
+                          [](const FileDesc &a, const FileDesc &b) {
+                              return a.min_key < b.min_key;
+                          });
+                int64_t rows = 0;
+                for (size_t i = 0; i < lf.size(); i++) {
+                    rows += lf[i].row_count;
+                    if (i > 0 && lf[i].min_key <= lf[i - 1].max_key) {
+                        set_error("lookup level %d: files %s and %s overlap "
+                                  "in key range (a level above 0 is one "
+                                  "sorted run)", kv.first,
+                                  lf[i - 1].path.c_str(), lf[i].path.c_str());
+                        return nullptr;
+                    }
+                }
+                if (rows >= ((int64_t)1 << PMH_ROW_BITS)) {
+                    set_error("lookup level %d totals %lld rows >= 2^%d "
+                              "rows-per-run limit", kv.first,
+                              (long long)rows, PMH_ROW_BITS);
+                    return nullptr;
+                }
+            }
+            Section &ls = plan->lookup_sec;
+            ls.runs.resize(by_level.size());
+            size_t li = 0;
+            for (auto &kv : by_level)  // std::map: ascending level
+                if (!stage_run(plan.get(), kv.second, ls.runs[li++]))
+                    return nullptr;
+            if (!build_decode_tables(plan.get(), ls)) {
+                set_error("device allocation failed for lookup levels");
+                return nullptr;
+            }
+            // decode once: the levels stay resident (and decoded) across
+            // sections and pmh_plan_reset
+            const char *dwhat = "decode";
+            hipError_t de = launch_section_decode(plan.get(), ls,
+                                                  plan->stream, &dwhat);
+            if (de == hipSuccess) de = hipStreamSynchronize(plan->stream);
+            if (de != hipSuccess) {
+                set_error("lookup levels %s: %s", dwhat,
+                          hipGetErrorString(de));
+                return nullptr;
+            }
+        }
         for (auto &sec_files : sections) {
             Section sec;
             if ((int)sec_files.size() > PMH_MAX_RUNS) {
@@ -3547,6 +3784,9 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             for (auto &run : sec.runs)
                 for (int c = 0; c < n_cols; c++)
                     if (run.cols[c].has_nulls) plan->col_nullable[c] = true;
+        for (auto &run : plan->lookup_sec.runs)
+            for (int c = 0; c < n_cols; c++)
+                if (run.cols[c].has_nulls) plan->col_nullable[c] = true;
         plan->out_valid.assign(n_cols, nullptr);
         std::vector<uint8_t> nul(n_cols, 0);
         for (int c = 0; c < n_cols; c++) {
@@ -3725,9 +3965,11 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
     // ev: 0 start, 1 decode done, 2 partition done, 3 merge done,
     //     4 scan done, 5 emit done
 
+    hipEvent_t ev_lk = nullptr;  // lookup probe done (lookup changelog)
     auto fail = [&](const char *what, hipError_t e) -> int64_t {
         set_error("%s: %s", what, hipGetErrorString(e));
         for (auto &evv : ev) (void)hipEventDestroy(evv);
+        if (ev_lk) (void)hipEventDestroy(ev_lk);
         return -1;
     };
 
@@ -3736,57 +3978,10 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
     // launch each across every run-column — the per-run-column launches
     // serialized ~350 small kernels per step on C3), plus parquet
     // dictionary materialization per chunk
-    if (sec.any_decode) {
-        if (sec.n_rlev2) {
-            hipError_t e = pmh_launch_rlev2(sec.rlev2_all, sec.n_rlev2, st);
-            if (e != hipSuccess) return fail("rlev2", e);
-        }
-        if (sec.n_delta) {
-            hipError_t e = pmh_launch_delta_sum(sec.delta_all, sec.n_delta,
-                                                sec.delta_sums, st);
-            if (e == hipSuccess)
-                e = pmh_launch_delta_scan(sec.dstreams_all, sec.n_dstreams,
-                                          sec.delta_sums, sec.delta_bases,
-                                          st);
-            if (e == hipSuccess)
-                e = pmh_launch_delta_emit(sec.delta_all, sec.n_delta,
-                                          sec.delta_bases, st);
-            if (e != hipSuccess) return fail("delta", e);
-        }
-        for (auto &run : sec.runs) {
-            for (size_t c = 0; c < run.cols.size(); c++) {
-                RunCol &rc = run.cols[c];
-                int es = p->cols[c].stored_esize;
-                if (!rc.dict_encoded && rc.gathers.empty()) continue;
-                if (rc.dict_encoded) {
-                    hipError_t e = pmh_launch_rle_decode(
-                        rc.rle_dev, (int64_t)rc.rle_host.size(), rc.ids_dev,
-                        st);
-                    if (e != hipSuccess) return fail("rle_decode", e);
-                }
-                for (const GatherTask &gt : rc.gathers) {
-                    if (!gt.n) continue;
-                    uint8_t *dst = gt.to_dense
-                                       ? (uint8_t *)rc.dense_dev
-                                       : (uint8_t *)rc.contig;
-                    // in_place: ORC dictionary-string LOCAL ids were
-                    // RLEv2-decoded at the target already; remap to global
-                    const int32_t *ids =
-                        gt.in_place
-                            ? (const int32_t *)(dst + gt.start * es)
-                            : rc.ids_dev + gt.start;
-                    hipError_t e = pmh_launch_dict_gather(
-                        ids, gt.dict_dev, gt.n, dst + gt.start * es, es,
-                        st);
-                    if (e != hipSuccess) return fail("dict_gather", e);
-                }
-            }
-        }
-        if (sec.n_def) {
-            hipError_t e =
-                pmh_launch_level_scatter(sec.def_all, sec.n_def, st);
-            if (e != hipSuccess) return fail("level_scatter", e);
-        }
+    {
+        const char *dwhat = "decode";
+        hipError_t de = launch_section_decode(p, sec, st, &dwhat);
+        if (de != hipSuccess) return fail(dwhat, de);
     }
     if (p->composite_key) {
         // rebuilt per pass (decode-derived, like the validity masks)
@@ -3843,7 +4038,7 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
                 sec.rlens + lo, kb, sec.cuts, btiles, PMH_TILE_ROWS, bflags,
                 sec.rtombs ? sec.rtombs + lo : nullptr, sec.winners,
                 sec.tile_counts, sec.group_start, sec.err_dev, nullptr, 0,
-                nullptr, nullptr, st);
+                nullptr, nullptr, nullptr, nullptr, st);
             if (hb != hipSuccess) return fail("hier merge", hb);
             hb = pmh_launch_scan_tiles(sec.tile_counts, btiles,
                                        sec.tile_offsets, sec.lens_dev + b,
@@ -3961,14 +4156,26 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
         }
         goto collect;
     }
+    if (p->lookup) {
+        // point lookup into the upper levels for every level-0 row, before
+        // the merge walk consumes the probe words (timed as lookup_ms)
+        (void)hipEventCreate(&ev_lk);
+        e = pmh_launch_lookup_probe(sec.key_cols, sec.lens_dev, sec.probe_off,
+                                    k, sec.n_lookup, sec.probe_max_rows,
+                                    sec.probe_words, st);
+        if (e != hipSuccess) return fail("lookup_probe", e);
+        (void)hipEventRecord(ev_lk, st);
+    }
     e = pmh_launch_merge_tiles(sec.key_cols, sec.seq_cols, sec.kind_cols,
                                sec.lens_dev, k, sec.cuts, n_tiles_eff,
                                PMH_TILE_ROWS,
-                               flags | (p->cl_row_dedup ? 128 : 0),
+                               flags | (p->cl_row_dedup ? 128 : 0) |
+                                   (p->lookup ? PMH_FLAG_LOOKUP : 0),
                                sec.tombs_dev, sec.winners,
                                sec.tile_counts, sec.group_start, sec.err_dev,
                                sec.run_levels, p->max_level, sec.cl_entries,
-                               sec.cl_counts, st);
+                               sec.cl_counts, sec.probe_words, sec.probe_off,
+                               st);
     if (e != hipSuccess) return fail("merge_tiles", e);
     (void)hipEventRecord(ev[3], st);
     e = pmh_launch_scan_tiles(sec.tile_counts, n_tiles_eff, sec.tile_offsets,
@@ -4075,7 +4282,11 @@ collect:
     p->stats.decode_ms += ms;
     (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
     p->stats.partition_ms += ms;
-    (void)hipEventElapsedTime(&ms, ev[2], ev[3]);
+    if (ev_lk) {
+        (void)hipEventElapsedTime(&ms, ev[2], ev_lk);
+        p->stats.lookup_ms += ms;
+    }
+    (void)hipEventElapsedTime(&ms, ev_lk ? ev_lk : ev[2], ev[3]);
     p->stats.merge_ms += ms;
     (void)hipEventElapsedTime(&ms, ev[3], ev[4]);
     p->stats.scan_ms += ms;
@@ -4084,6 +4295,7 @@ collect:
     (void)hipEventElapsedTime(&ms, ev[0], ev[5]);
     p->stats.total_device_ms += ms;
     for (auto &evv : ev) (void)hipEventDestroy(evv);
+    if (ev_lk) (void)hipEventDestroy(ev_lk);
 
     p->stats.rows_in += sec.total_rows;
     p->stats.rows_out += total;
@@ -4383,6 +4595,48 @@ char *pmh_debug_footer_json(const char *path) {
     }
     out += "]}";
     return strdup(out.c_str());
+}
+
+// Host entry to the lookup search core (lookup_core.h) shared with
+// k_lookup_probe: queries are walked in chunks of PLK_CHUNK like the
+// kernel's workgroups — one window per level from the chunk's smallest and
+// largest key, then a windowed bisection per query.
+int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
+                           const int64_t *level_rows, const int64_t *queries,
+                           int64_t n_queries, int32_t *out_level,
+                           int64_t *out_row) {
+    if (n_levels < 0 || n_levels > PMH_MAX_RUNS || n_queries < 0 ||
+        (n_levels > 0 && (!level_keys || !level_rows)) ||
+        (n_queries > 0 && (!queries || !out_level || !out_row))) {
+        set_error("pmh_debug_lookup_probe: bad arguments (0..%d levels)",
+                  PMH_MAX_RUNS);
+        return -1;
+    }
+    std::vector<PlkLevel> lv(n_levels);
+    for (int l = 0; l < n_levels; l++) {
+        if (level_rows[l] < 0 || (level_rows[l] > 0 && !level_keys[l])) {
+            set_error("pmh_debug_lookup_probe: level %d is malformed", l);
+            return -1;
+        }
+        lv[l] = PlkLevel{(uint64_t)(uintptr_t)level_keys[l], level_rows[l],
+                         8, 0};
+    }
+    std::vector<int64_t> wlo(n_levels), whi(n_levels);
+    for (int64_t base = 0; base < n_queries; base += PLK_CHUNK) {
+        const int64_t cnt = std::min<int64_t>(PLK_CHUNK, n_queries - base);
+        const auto mm =
+            std::minmax_element(queries + base, queries + base + cnt);
+        for (int l = 0; l < n_levels; l++)
+            plk_window(lv[l], *mm.first, *mm.second, &wlo[l], &whi[l]);
+        for (int64_t i = base; i < base + cnt; i++) {
+            int64_t row = -1;
+            int l = plk_probe(lv.data(), n_levels, wlo.data(), whi.data(),
+                              queries[i], &row);
+            out_level[i] = l;
+            out_row[i] = l < 0 ? -1 : row;
+        }
+    }
+    return 0;
 }
 
 int pmh_debug_interval_partition(int n, const int64_t *min_keys,

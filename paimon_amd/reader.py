@@ -53,7 +53,8 @@ class _Stats(ctypes.Structure):
                 ("total_device_ms", ctypes.c_double),
                 ("h2d_ms", ctypes.c_double),
                 ("path_mode", ctypes.c_int64),
-                ("gpu_zstd_pages", ctypes.c_int64)]
+                ("gpu_zstd_pages", ctypes.c_int64),
+                ("lookup_ms", ctypes.c_double)]
 
 
 _lib = None
@@ -102,6 +103,12 @@ def load_lib(required=True):
         ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
         ctypes.POINTER(ctypes.c_int32)]
+    lib.pmh_debug_lookup_probe.restype = ctypes.c_int
+    lib.pmh_debug_lookup_probe.argtypes = [
+        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+        ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+        ctypes.POINTER(ctypes.c_int64)]
     _lib = lib
     return lib
 
@@ -286,6 +293,29 @@ def interval_partition(min_keys, max_keys):
     return list(sec), list(run), ns
 
 
+def debug_lookup_probe(levels, queries):
+    """Point lookup of `queries` into `levels` (a list of ascending unique
+    int64 key arrays, searched in list order; first hit wins) through the
+    host entry of the search core that k_lookup_probe runs on the GPU.
+    Returns (level, row) int arrays; -1 where no level holds the key."""
+    lib = load_lib()
+    lv = [np.ascontiguousarray(a, dtype=np.int64) for a in levels]
+    q = np.ascontiguousarray(queries, dtype=np.int64)
+    n = len(lv)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in lv])
+    rows = (ctypes.c_int64 * max(n, 1))(*[len(a) for a in lv])
+    out_level = np.empty(len(q), dtype=np.int32)
+    out_row = np.empty(len(q), dtype=np.int64)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    rc = lib.pmh_debug_lookup_probe(
+        n, ptrs, rows, q.ctypes.data_as(i64p), len(q),
+        out_level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        out_row.ctypes.data_as(i64p))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out_level, out_row
+
+
 class Session:
     def __init__(self, device=0):
         self.lib = load_lib()
@@ -315,7 +345,8 @@ class MergeReadPlan:
                  remove_record_on_delete=False, sequence_groups=None,
                  ignore_retract=None, sequence_fields=None,
                  changelog_producer=None, changelog_row_dedup=False,
-                 max_level=None, sort_engine="loser-tree", filters=None):
+                 max_level=None, sort_engine="loser-tree", filters=None,
+                 lookup_files=None):
         self.lib = session.lib
         desc = {
             "key_cols": key_cols,
@@ -351,10 +382,14 @@ class MergeReadPlan:
         if changelog_producer:
             # changelog-producer = full-compaction
             # (FullChangelogMergeFunctionWrapper; max_level = num-levels - 1)
+            # or lookup (LookupChangelogMergeFunctionWrapper; lookup_files =
+            # the data files of the levels above the output level)
             desc["changelog_producer"] = changelog_producer
             desc["changelog_row_deduplicate"] = bool(changelog_row_dedup)
             desc["max_level"] = int(max_level if max_level is not None
                                     else -1)
+        if lookup_files:
+            desc["lookup_files"] = list(lookup_files)
         self.h = self.lib.pmh_plan_create(session.h,
                                           json.dumps(desc).encode())
         if not self.h:
@@ -406,9 +441,9 @@ class MergeReadPlan:
 
     def read_changelog(self):
         """Changelog batch of the LAST read_next (changelog_producer =
-        "full-compaction"): dict name -> numpy array (host output), may be
-        empty. Same schema as the main batch; _VALUE_KIND carries the
-        changelog RowKind (0=+I, 1=-U, 2=+U, 3=-D)."""
+        "full-compaction" or "lookup"): dict name -> numpy array (host
+        output), may be empty. Same schema as the main batch; _VALUE_KIND
+        carries the changelog RowKind (0=+I, 1=-U, 2=+U, 3=-D)."""
         b = _Batch()
         n = self.lib.pmh_changelog_next(self.h, ctypes.byref(b))
         if n < 0:
