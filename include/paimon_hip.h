@@ -238,6 +238,14 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
                            int64_t n_queries, int32_t *out_level,
                            int64_t *out_row);
 
+/* Parse one JSON number the way the plan descriptor's numbers are parsed
+ * (minKey/maxKey, rowCount, integer filter literals): a token without '.',
+ * 'e' or 'E' is an exact int64, a fractional token rounds to nearest, an
+ * integer outside int64 is an error. Writes the value to *out; returns 0,
+ * or -1 with pmh_last_error() set. CPU-only debug entry pinning the parser
+ * over the whole int64 range. */
+int pmh_debug_json_i64(const char *text, int64_t *out);
+
 /* Restatement of IntervalPartition.partition() for int64 keys
  * (mergetree/compact/IntervalPartition.java:67-125): given n files'
  * (minKey, maxKey), writes section id and run-within-section id per file

@@ -1,6 +1,14 @@
 // Minimal JSON parser/serializer for the plan descriptor — no dependencies.
+//
+// Numbers: a token without '.', 'e' or 'E' is an integer and is kept EXACTLY
+// as an int64 next to its double (minKey/maxKey, packed composite keys and
+// int64 filter literals use the whole 64-bit range, which a double cannot
+// hold above 2^53); an integer token outside int64 is rejected as "bad JSON
+// number". as_i64() returns the exact value for integer tokens and the
+// rounded double for fractional ones; .num always holds the double.
 #pragma once
 
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <map>
@@ -15,6 +23,8 @@ struct Json {
     enum Type { NUL, BOOL, NUM, STR, ARR, OBJ } type = NUL;
     bool b = false;
     double num = 0;
+    int64_t inum = 0;     // exact value of an integer token
+    bool is_int = false;  // token had no '.', 'e' or 'E'
     std::string str;
     std::vector<Json> arr;
     std::map<std::string, Json> obj;
@@ -26,7 +36,8 @@ struct Json {
         return it == obj.end() ? null_json : it->second;
     }
     int64_t as_i64(int64_t dflt = 0) const {
-        return type == NUM ? (int64_t)llround(num) : dflt;
+        if (type != NUM) return dflt;
+        return is_int ? inum : (int64_t)llround(num);
     }
     bool as_bool(bool dflt = false) const { return type == BOOL ? b : dflt; }
     std::string as_str(const std::string &dflt = "") const {
@@ -123,6 +134,18 @@ class JsonParser {
         j.type = Json::NUM;
         j.num = strtod(p_, &end);
         if (end == p_) throw std::runtime_error("bad JSON number");
+        j.is_int = true;
+        for (const char *q = p_; q < end; q++)
+            if (*q != '-' && *q != '+' && (*q < '0' || *q > '9'))
+                j.is_int = false;  // fraction, exponent, inf/nan, hex
+        if (j.is_int) {
+            char *iend = nullptr;
+            errno = 0;
+            long long v = strtoll(p_, &iend, 10);
+            if (iend != end || errno == ERANGE)
+                throw std::runtime_error("bad JSON number");
+            j.inum = (int64_t)v;
+        }
         p_ = end;
         return j;
     }

@@ -4639,6 +4639,28 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
     return 0;
 }
 
+// The plan descriptor's number rule, exposed on its own: `text` goes through
+// the same JsonParser and as_i64() that read minKey/maxKey and the integer
+// filter literals.
+int pmh_debug_json_i64(const char *text, int64_t *out) {
+    if (!text || !out) {
+        set_error("pmh_debug_json_i64: null argument");
+        return -1;
+    }
+    try {
+        Json j = JsonParser(text).parse();
+        if (j.type != Json::NUM) {
+            set_error("pmh_debug_json_i64: not a JSON number");
+            return -1;
+        }
+        *out = j.as_i64();
+    } catch (const std::exception &e) {
+        set_error("pmh_debug_json_i64: %s", e.what());
+        return -1;
+    }
+    return 0;
+}
+
 int pmh_debug_interval_partition(int n, const int64_t *min_keys,
                                  const int64_t *max_keys, int32_t *out_section,
                                  int32_t *out_run) {

@@ -109,6 +109,9 @@ def load_lib(required=True):
         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
         ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
         ctypes.POINTER(ctypes.c_int64)]
+    lib.pmh_debug_json_i64.restype = ctypes.c_int
+    lib.pmh_debug_json_i64.argtypes = [ctypes.c_char_p,
+                                       ctypes.POINTER(ctypes.c_int64)]
     _lib = lib
     return lib
 
@@ -291,6 +294,17 @@ def interval_partition(min_keys, max_keys):
     if ns < 0:
         raise RuntimeError(last_error())
     return list(sec), list(run), ns
+
+
+def debug_json_i64(text):
+    """Parse one JSON number string through the plan descriptor's parser
+    (JsonParser + as_i64) and return the int64 it yields; raises on a
+    malformed or out-of-range number."""
+    lib = load_lib()
+    out = ctypes.c_int64(0)
+    if lib.pmh_debug_json_i64(str(text).encode(), ctypes.byref(out)) != 0:
+        raise RuntimeError(last_error())
+    return out.value
 
 
 def debug_lookup_probe(levels, queries):
