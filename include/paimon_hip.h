@@ -219,6 +219,32 @@ int64_t pmh_debug_zstd_enc_cpu(const void *src, int64_t n, void *dst,
 int64_t pmh_debug_zstd_enc_gpu(const void *src, int64_t n, void *dst,
                                int64_t cap);
 
+/* Decode one ORC integer stream through the product's own decoders, so
+ * tests can force every sub-encoding, width and alignment instead of taking
+ * what a file writer happens to pick.
+ *   kind: 0 = RLEv2 signed, 1 = RLEv2 unsigned, 2 = byte-RLE (tinyint).
+ *   mode 0, host twin (no GPU): the host decoder that reads string LENGTH
+ *     streams; kind 1 only. n_values < 0 decodes until the stream is
+ *     exhausted (the DICTIONARY_V2 LENGTH call). Writes up to out_cap
+ *     uint64 values to `out`; returns the number of values decoded.
+ *   mode 1, prescan only (no GPU): walks the stream into device work chunks
+ *     against a dummy device base; returns the number of chunks. `out` is
+ *     unused.
+ *   mode 2, device path: uploads the stream as staging does (16-byte tail
+ *     pad) at src_shift (0..7) bytes past an 8-byte-aligned device address,
+ *     prescans, launches k_rlev2 once over all chunks and copies n_values
+ *     elements of out_esize (4 or 8) bytes to `out` (out_cap >= n_values
+ *     elements). The device output sits between two 64-element guard zones
+ *     and is pre-filled, like them, with the byte 0xA5, so an element the
+ *     kernel never wrote reads back as 0xA5A5... Returns n_values. Owns its
+ *     device memory; needs no session.
+ * Returns -1 with pmh_last_error() set on a malformed or truncated stream,
+ * bad arguments or a HIP error, and -2 when the kernel changed a guard
+ * zone (the output is still copied out). */
+int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
+                           int kind, int out_esize, int mode,
+                           int64_t src_shift, void *out, int64_t out_cap);
+
 /* Parse one deletion vector from a DV index file slice (DeletionFile
  * {path, offset, length}; BitmapDeletionVector.java:98-112 wrapper around
  * the portable Roaring serialization). Writes up to `cap` deleted

@@ -1170,10 +1170,21 @@ static bool load_file(const std::string &path, StagedFile &sf) {
 // that staging needs on the host (string id-ification). Restates the ORC
 // v1 spec's RLEv2 (same arithmetic as k_rlev2;
 // orc/impl/RunLengthIntegerReaderV2.java is the reference consumer).
-static int rlev2_width(int enc) {
-    static const int tbl[8] = {26, 28, 30, 32, 40, 48, 56, 64};
-    if (enc < 24) return enc + 1;
-    return tbl[enc - 24];
+// The spec's 5-bit width code -> bit width table ("fixed bit sizes"): the one
+// copy both the host decoder and the prescan read.
+static const int RLEV2_FBS[32] = {1,  2,  3,  4,  5,  6,  7,  8,
+                                  9,  10, 11, 12, 13, 14, 15, 16,
+                                  17, 18, 19, 20, 21, 22, 23, 24,
+                                  26, 28, 30, 32, 40, 48, 56, 64};
+
+static int rlev2_width(int enc) { return RLEV2_FBS[enc & 31]; }
+
+// Smallest encodable width >= n: PATCHED_BASE packs each (gap, patch) entry
+// at closest_fixed_bits(pgw + pw) bits.
+static int rlev2_closest_fixed_bits(int n) {
+    for (int i = 0; i < 32; i++)
+        if (RLEV2_FBS[i] >= n) return RLEV2_FBS[i];
+    return 64;
 }
 
 static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
@@ -1221,7 +1232,7 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
             int pgw = ((s[p + 3] >> 5) & 7) + 1;
             int pll = s[p + 3] & 31;
             int64_t q = p + 4;
-            if (q + bw > len) return false;
+            if (q + bw > len || pw + pgw > 64) return false;
             uint64_t braw = 0;
             for (int i = 0; i < bw; i++) braw = (braw << 8) | s[q + i];
             int64_t base = (int64_t)braw;
@@ -1229,8 +1240,7 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
             if (braw & sign) base = -(int64_t)(braw & (sign - 1));
             q += bw;
             int64_t dbytes = ((int64_t)cnt * w + 7) / 8;
-            int pbits = pgw * 8 + pw;
-            pbits = ((pbits + 7) / 8) * 8;
+            int pbits = rlev2_closest_fixed_bits(pgw + pw);
             int64_t pbytes = ((int64_t)pll * pbits + 7) / 8;
             if (q + dbytes + pbytes > len) return false;
             std::vector<uint64_t> vals(cnt);
@@ -1285,7 +1295,9 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
                     out.push_back((uint64_t)cur);
                 }
             } else {
-                int64_t nbytes = ((int64_t)(cnt - 2) * w + 7) / 8;
+                // a run of 1 or 2 values carries no packed deltas
+                int64_t nbytes =
+                    cnt > 2 ? ((int64_t)(cnt - 2) * w + 7) / 8 : 0;
                 if (q + nbytes > len) return false;
                 for (int i = 2; i < cnt; i++) {
                     int64_t d = (int64_t)bits_be(q, (int64_t)(i - 2) * w, w);
@@ -1304,11 +1316,14 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
                           int is_signed, int out_esize, int dense_target,
                           uint64_t dev_base, int64_t dense0,
                           std::vector<Rlev2Chunk> &out) {
-    static const int fbs[32] = {1,  2,  3,  4,  5,  6,  7,  8,
-                                9,  10, 11, 12, 13, 14, 15, 16,
-                                17, 18, 19, 20, 21, 22, 23, 24,
-                                26, 28, 30, 32, 40, 48, 56, 64};
+    const int *fbs = RLEV2_FBS;
     int64_t p = 0, cnt = 0;
+    // every header byte is checked against len BEFORE it is read
+    auto need = [&](int64_t nbytes) -> bool {
+        if (p + nbytes <= len) return true;
+        set_error("RLEv2 run header truncated");
+        return false;
+    };
     auto uvarint = [&](bool &ok) -> uint64_t {
         uint64_t v = 0;
         int shift = 0;
@@ -1335,6 +1350,7 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
         if (enc == 0) {  // SHORT_REPEAT: host decodes the literal
             int w = ((first >> 3) & 7) + 1;
             int rep = (first & 7) + 3;
+            if (!need(w)) return false;
             uint64_t raw = 0;
             for (int i = 0; i < w; i++) raw = (raw << 8) | s[p++];
             c.kind = 0;
@@ -1344,6 +1360,7 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
             c.count = rep;
             cnt += rep;
         } else if (enc == 1) {  // DIRECT
+            if (!need(1)) return false;
             int width = fbs[(first >> 1) & 0x1f];
             int count = (int)(((first & 1) << 8) | s[p++]) + 1;
             c.kind = 1;
@@ -1353,6 +1370,7 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
             p += ((int64_t)count * width + 7) / 8;
             cnt += count;
         } else if (enc == 2) {  // PATCHED_BASE
+            if (!need(3)) return false;
             int width = fbs[(first >> 1) & 0x1f];
             int count = (int)(((first & 1) << 8) | s[p++]) + 1;
             uint8_t third = s[p++], fourth = s[p++];
@@ -1360,6 +1378,11 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
             int pw = fbs[third & 0x1f];
             int pgw = ((fourth >> 5) & 7) + 1;
             int pl = fourth & 0x1f;
+            if (!need(bw)) return false;
+            if (pw + pgw > 64) {
+                set_error("RLEv2 patch entry wider than 64 bits");
+                return false;
+            }
             uint64_t braw = 0;
             for (int i = 0; i < bw; i++) braw = (braw << 8) | s[p++];
             uint64_t smask = 1ull << (bw * 8 - 1);
@@ -1370,9 +1393,7 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
                                     : (int64_t)braw;
             c.src = dev_base + p;
             p += ((int64_t)count * width + 7) / 8;
-            int cfb = 64;
-            for (int i = 0; i < 32; i++)
-                if (fbs[i] >= pw + pgw) { cfb = fbs[i]; break; }
+            int cfb = rlev2_closest_fixed_bits(pw + pgw);
             c.patch_src = dev_base + p;
             c.patch_pl = (uint16_t)pl;
             c.patch_pw = (uint8_t)pw;
@@ -1383,6 +1404,7 @@ static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
         } else {  // DELTA
             int wcode = (first >> 1) & 0x1f;
             int width = wcode == 0 ? 0 : fbs[wcode];
+            if (!need(1)) return false;
             int count = (int)(((first & 1) << 8) | s[p++]) + 1;
             bool ok = true;
             uint64_t braw = uvarint(ok);
@@ -1432,6 +1454,10 @@ static bool prescan_byterle(const uint8_t *s, int64_t len, int64_t n_values,
         c.dense_target = (uint8_t)dense_target;
         c.out_start = dense0 + cnt;
         if (h >= 0) {
+            if (p >= len) {
+                set_error("byte-RLE run truncated");
+                return false;
+            }
             c.kind = 4;
             c.base = (int8_t)s[p++];
             c.count = (int32_t)std::min<int64_t>(h + 3, n_values - cnt);
@@ -1439,6 +1465,11 @@ static bool prescan_byterle(const uint8_t *s, int64_t len, int64_t n_values,
             c.kind = 5;
             c.src = dev_base + p;
             c.count = (int32_t)std::min<int64_t>(-(int64_t)h, n_values - cnt);
+            // the kernel reads c.count literal bytes: they must be there
+            if (p + c.count > len) {
+                set_error("byte-RLE literal truncated");
+                return false;
+            }
             p += -(int64_t)h;
         }
         cnt += c.count;
@@ -4505,6 +4536,132 @@ int64_t pmh_debug_zstd_enc_gpu(const void *src, int64_t n, void *dst,
     if ((int64_t)outs[0].size() > cap) return PZ_ERR_DST_SMALL;
     memcpy(dst, outs[0].data(), outs[0].size());
     return (int64_t)outs[0].size();
+}
+
+// Stream-level entry to the three ORC integer decoders (host_rlev2_u, the
+// prescan walk, k_rlev2): see paimon_hip.h. Calls the very functions the
+// plan calls.
+int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
+                           int kind, int out_esize, int mode,
+                           int64_t src_shift, void *out, int64_t out_cap) {
+    const uint8_t *s = (const uint8_t *)stream;
+    if ((!s && len > 0) || len < 0 || kind < 0 || kind > 2 || mode < 0 ||
+        mode > 2 || (out_cap > 0 && !out)) {
+        set_error("pmh_debug_orc_ints: bad arguments");
+        return -1;
+    }
+    if (mode == 0) {  // host twin
+        if (kind != 1) {
+            set_error("pmh_debug_orc_ints: the host decoder is unsigned "
+                      "RLEv2 only (kind 1)");
+            return -1;
+        }
+        std::vector<uint64_t> v;
+        if (!host_rlev2_u(s, len, n_values, v)) {
+            set_error("pmh_debug_orc_ints: host RLEv2 decode failed");
+            return -1;
+        }
+        int64_t n = std::min<int64_t>((int64_t)v.size(), out_cap);
+        if (n > 0) memcpy(out, v.data(), (size_t)n * 8);
+        return (int64_t)v.size();
+    }
+    if (n_values < 0 || (out_esize != 4 && out_esize != 8) ||
+        src_shift < 0 || src_shift > 7) {
+        set_error("pmh_debug_orc_ints: bad arguments (n_values >= 0, "
+                  "out_esize 4|8, src_shift 0..7)");
+        return -1;
+    }
+    auto prescan = [&](uint64_t dev_base, std::vector<Rlev2Chunk> &ch) {
+        return kind == 2 ? prescan_byterle(s, len, n_values, out_esize, 0,
+                                           dev_base, 0, ch)
+                         : prescan_rlev2(s, len, n_values, kind == 0,
+                                         out_esize, 0, dev_base, 0, ch);
+    };
+    std::vector<Rlev2Chunk> chunks;
+    if (mode == 1) {  // prescan only: dummy device base
+        if (!prescan(0x1000, chunks)) return -1;
+        return (int64_t)chunks.size();
+    }
+    if (out_cap < n_values) {
+        set_error("pmh_debug_orc_ints: out_cap < n_values");
+        return -1;
+    }
+    if (n_values == 0) return 0;
+    // device path: stream at an 8-byte-aligned address + src_shift with the
+    // 16-byte tail pad staging gives it; output between two guard zones
+    const int64_t GUARD = 64;  // elements, each side
+    const uint8_t FILL = 0xA5;
+    uint8_t *d_src = nullptr, *d_out = nullptr;
+    Rlev2Chunk *d_chunks = nullptr;
+    const size_t out_bytes = (size_t)(n_values + 2 * GUARD) * out_esize;
+    std::vector<uint8_t> back(out_bytes);
+    int64_t rc = -1;
+    do {
+        if (hipMalloc(&d_src, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMalloc(&d_out, out_bytes) != hipSuccess) {
+            set_error("pmh_debug_orc_ints: hipMalloc failed");
+            break;
+        }
+        if (((uint64_t)d_src & 7) != 0) {
+            set_error("pmh_debug_orc_ints: device allocation not 8-aligned");
+            break;
+        }
+        if (hipMemset(d_src, 0, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMemset(d_out, FILL, out_bytes) != hipSuccess ||
+            (len && hipMemcpy(d_src + src_shift, s, (size_t)len,
+                              hipMemcpyHostToDevice) != hipSuccess)) {
+            set_error("pmh_debug_orc_ints: H2D failed");
+            break;
+        }
+        if (!prescan((uint64_t)(d_src + src_shift), chunks)) break;
+        // the prescan may overshoot n_values only in an RLEv2 stream's last
+        // run; the plan sizes its buffers from the file's row count, so a
+        // stream that decodes past n_values is refused here, not run
+        int64_t total = 0;
+        for (auto &c : chunks) {
+            c.out_addr = (uint64_t)(d_out + GUARD * out_esize);
+            total = std::max<int64_t>(total, c.out_start + c.count);
+        }
+        if (total > n_values) {
+            set_error("pmh_debug_orc_ints: stream holds %lld values, more "
+                      "than n_values %lld", (long long)total,
+                      (long long)n_values);
+            break;
+        }
+        if (hipMalloc(&d_chunks, chunks.size() * sizeof(Rlev2Chunk)) !=
+                hipSuccess ||
+            hipMemcpy(d_chunks, chunks.data(),
+                      chunks.size() * sizeof(Rlev2Chunk),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("pmh_debug_orc_ints: chunk upload failed");
+            break;
+        }
+        hipError_t e =
+            pmh_launch_rlev2(d_chunks, (int64_t)chunks.size(), nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess)
+            e = hipMemcpy(back.data(), d_out, out_bytes,
+                          hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_error("pmh_debug_orc_ints: k_rlev2: %s",
+                      hipGetErrorString(e));
+            break;
+        }
+        rc = n_values;
+        const size_t g = (size_t)GUARD * out_esize;
+        for (size_t i = 0; i < g; i++)
+            if (back[i] != FILL || back[out_bytes - 1 - i] != FILL) {
+                set_error("pmh_debug_orc_ints: k_rlev2 wrote outside its "
+                          "output (guard zone changed)");
+                rc = -2;
+                break;
+            }
+        memcpy(out, back.data() + g, (size_t)n_values * out_esize);
+    } while (0);
+    if (d_src) (void)hipFree(d_src);
+    if (d_out) (void)hipFree(d_out);
+    if (d_chunks) (void)hipFree(d_chunks);
+    return rc;
 }
 
 int64_t pmh_debug_snappy(const void *src, int64_t n, void *dst, int64_t cap) {

@@ -281,6 +281,49 @@ def debug_zstd_enc_gpu(data, cap=None):
     return bytes(out[:n])
 
 
+ORC_INTS_SIGNED, ORC_INTS_UNSIGNED, ORC_INTS_BYTE = 0, 1, 2
+ORC_INTS_HOST, ORC_INTS_PRESCAN, ORC_INTS_DEVICE = 0, 1, 2
+
+
+def debug_orc_ints(stream, n_values, kind, mode, out_esize=8, src_shift=0):
+    """One ORC integer stream through the product's decoders
+    (pmh_debug_orc_ints). mode ORC_INTS_HOST returns the host LENGTH
+    decoder's values as uint64 (n_values < 0: until the stream ends);
+    ORC_INTS_PRESCAN returns the number of device chunks; ORC_INTS_DEVICE
+    returns what k_rlev2 wrote, as int32/int64 by out_esize (needs a GPU).
+    Raises RuntimeError on a rejected stream; a device store outside the
+    output raises AssertionError."""
+    lib = load_lib()
+    lib.pmh_debug_orc_ints.restype = ctypes.c_int64
+    lib.pmh_debug_orc_ints.argtypes = [
+        ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64]
+    stream = bytes(stream)
+
+    def call(out, cap):
+        ptr = out.ctypes.data_as(ctypes.c_void_p) if out is not None else None
+        n = lib.pmh_debug_orc_ints(stream, len(stream), n_values, kind,
+                                   out_esize, mode, src_shift, ptr, cap)
+        if n == -2:
+            raise AssertionError(last_error())
+        if n < 0:
+            raise RuntimeError(last_error())
+        return n
+
+    if mode == ORC_INTS_PRESCAN:
+        return call(None, 0)
+    if mode == ORC_INTS_HOST:
+        n = call(None, 0) if n_values < 0 else n_values
+        out = np.empty(max(n, 1), dtype=np.uint64)
+        n = call(out, len(out))
+        return out[:n]
+    out = np.empty(max(n_values, 1),
+                   dtype=np.int32 if out_esize == 4 else np.int64)
+    call(out, len(out))
+    return out[:n_values]
+
+
 def interval_partition(min_keys, max_keys):
     """Returns (section_id, run_id) per input file, per the IntervalPartition
     restatement in libpaimon_hip (plan.cpp)."""

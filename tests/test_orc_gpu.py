@@ -2,12 +2,17 @@
 PRESENT decode on device, feeding the same merge pipeline — against the CPU
 oracle on ORC files written by pyarrow (the independent implementation)."""
 
+import os
+
 import numpy as np
 import pytest
+from pyarrow import orc as pa_orc
 
 from oracle import merge_dedup, partial_update_model
+from oracle import orc_light as ol
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
-from paimon_amd.datagen import gen_runs_dedup, gen_runs_partial_update, write_runs
+from paimon_amd.datagen import (gen_runs_dedup, gen_runs_partial_update,
+                                run_to_arrow, write_runs)
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +135,120 @@ class TestOrcPartialUpdate:
             if gm is None:
                 gm = np.ones(len(got[nm]), dtype=bool)
             assert (gm == em).all(), nm
+            assert (got[nm][em] == ev[em]).all(), nm
+
+
+def _alternating(n):
+    return np.arange(n) % 2 == 0
+
+
+def _then_null(n_valid, tail):
+    """n_valid valid rows (whole 0xFF PRESENT bytes), one null, tail valid."""
+    return np.r_[np.ones(n_valid, bool), False, np.ones(tail, bool)]
+
+
+# name -> (validity of run 0, validity of run 1, stripe_size or None).
+# PRESENT is byte-RLE over MSB-first bit-packed bytes; a byte run holds at
+# most 130 bytes = 1040 rows, so 1040 and 1048 rows of one repeated byte sit
+# on the edge between one run and a run plus one more byte.
+PRESENT_PATTERNS = {
+    "all_null": (np.zeros(1000, bool), np.zeros(1003, bool), None),
+    "no_nulls": (np.ones(1000, bool), np.ones(1003, bool), None),
+    "alternating_130_bytes": (_alternating(1040), ~_alternating(1040), None),
+    "alternating_131_bytes": (_alternating(1048), ~_alternating(1048), None),
+    "alternating_odd_rows": (_alternating(1043), ~_alternating(1045), None),
+    "null_run_then_valid_run": (np.arange(5003) >= 2500,
+                                np.arange(4999) < 2400, None),
+    "valid_130_bytes": (_then_null(1040, 6), ~_then_null(1040, 6), None),
+    "valid_131_bytes": (_then_null(1048, 2), ~_then_null(1048, 2), None),
+    # stripe_size 1: the writer cuts a stripe every 1024 rows, so the dense
+    # cursor carries over stripe boundaries; in the second case a stripe is
+    # all null, the next has no PRESENT stream at all, the last one is mixed
+    "two_stripes": (np.arange(2051) % 7 < 3, np.arange(1500) % 5 != 1, 1),
+    "stripes_null_full_mixed": (
+        np.r_[np.zeros(1024, bool), np.ones(1024, bool), _alternating(501)],
+        np.r_[np.ones(1024, bool), np.zeros(1024, bool), _alternating(77)],
+        1),
+}
+
+
+def _present_run_headers(path, column):
+    """Header bytes of the column's PRESENT byte-RLE runs, per stripe."""
+    fi = ol.parse_orc(path)
+    cid = fi.column_names.index(column) + 1
+    with open(path, "rb") as f:
+        raw = f.read()
+    out = []
+    for st in fi.stripes:
+        ps = ol.find_stream(st, cid, ol.STREAM_PRESENT)
+        heads = []
+        if ps is not None:
+            s, p = raw[ps.offset:ps.offset + ps.length], 0
+            while p < len(s):
+                heads.append(s[p])
+                p += 2 if s[p] < 128 else 1 + 256 - s[p]
+        out.append(heads)
+    return out
+
+
+class TestOrcPresentPatterns:
+    """Nullable int64 (v_k) and int32 (v_c0) columns whose PRESENT streams
+    have structure a random null mask never has: the boolean-RLE walk, its
+    hand-off to the level scatter and the dense (non-null) cursor, across
+    run-length edges, odd row counts and a stripe boundary."""
+
+    @pytest.mark.parametrize("name", list(PRESENT_PATTERNS))
+    def test_pattern(self, tmp_path, name):
+        v0, v1, stripe_size = PRESENT_PATTERNS[name]
+        rng = np.random.default_rng(91)
+        runs = []
+        n_all = len(v0) + len(v1)
+        seqs = rng.permutation(n_all).astype(np.int64)
+        lo = 0
+        for valid in (v0, v1):
+            n = len(valid)
+            keys = np.sort(rng.choice(n_all, n, replace=False)).astype(
+                np.int64)
+            runs.append({
+                "key": keys, "seq": seqs[lo:lo + n],
+                "kind": np.zeros(n, np.int8),
+                "values": [rng.integers(-2**62, 2**62, n),
+                           rng.integers(-2**31, 2**31, n).astype(np.int32)],
+                # the int32 column gets the mirrored pattern
+                "valid": [valid, valid[::-1].copy()]})
+            lo += n
+        metas = []
+        for i, run in enumerate(runs):
+            path = os.path.join(str(tmp_path), f"run-{i}.orc")
+            kw = {"stripe_size": stripe_size} if stripe_size else {}
+            pa_orc.write_table(run_to_arrow(run), path,
+                               compression="uncompressed", **kw)
+            metas.append({"path": path, "rowCount": len(run["key"]),
+                          "minKey": int(run["key"][0]),
+                          "maxKey": int(run["key"][-1]), "level": 0})
+        # the files must hold what the case is about
+        heads = [_present_run_headers(m["path"], "v_k") for m in metas]
+        if stripe_size:
+            assert all(len(h) >= 2 for h in heads), "one stripe only"
+        if name.endswith("130_bytes") or name.endswith("131_bytes"):
+            assert all(127 in h[0] for h in heads), "no 130-byte run"
+        if name == "no_nulls":
+            assert all(h == [[]] for h in heads)
+        r, w = merge_dedup(runs)
+        with Session(0) as s:
+            with MergeReadPlan(s, file_descs_from_metas(metas), KEY_COLS,
+                               _value_cols(1)) as plan:
+                got = _read_all(plan)
+        assert (got["_KEY_k"] ==
+                np.array([runs[a]["key"][b] for a, b in zip(r, w)])).all()
+        for c, nm in enumerate(("v_k", "v_c0")):
+            ev = np.array([runs[a]["values"][c][b] for a, b in zip(r, w)])
+            em = np.array([runs[a]["valid"][c][b] for a, b in zip(r, w)],
+                          bool)
+            gm = got.get(nm + "#valid")
+            if gm is None:
+                gm = np.ones(len(got[nm]), dtype=bool)
+            assert (gm.astype(bool) == em).all(), nm
             assert (got[nm][em] == ev[em]).all(), nm
 
 

@@ -11,8 +11,10 @@ import pyarrow.orc as orc
 import pytest
 
 from oracle import merge_dedup
+from oracle import orc_light as ol
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import gen_runs_dedup
+from tests import orc_streams as S
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +64,13 @@ def _check(tmp_path, dict_threshold, card=40, null_frac=0.0, n_runs=4,
     metas = _write_orc_str(runs, strs, str(tmp_path), dict_threshold,
                            null_masks=masks if null_frac else None,
                            compression=compression)
+    _read_and_compare(runs, strs, masks if null_frac else None, metas)
+
+
+def _read_and_compare(runs, strs, masks, metas):
+    """Merged-output parity of the string column against the oracle over
+    the source arrays (masks: per-run null masks or None)."""
+    null_frac = masks is not None
     rr, ww = merge_dedup(runs)
     exp_keys = np.array([runs[a]["key"][b] for a, b in zip(rr, ww)],
                         np.int64)
@@ -89,6 +98,71 @@ def _check(tmp_path, dict_threshold, card=40, null_frac=0.0, n_runs=4,
     live = ~exp_null
     dec = np.array([dicts[i].decode() for i in ids[live]])
     assert (dec == np.array(exp_str, dtype=object)[live].astype(str)).all()
+
+
+def _outlier_lengths(rng, n):
+    """Lengths 1..5 with about 2 % at 200..900: what makes the writer pick
+    PATCHED_BASE for a LENGTH stream."""
+    lens = rng.integers(1, 6, n)
+    big = rng.random(n) < 0.02
+    lens[big] = rng.integers(200, 901, int(big.sum()))
+    return lens
+
+
+def _random_words(rng, lens):
+    alpha = np.array(list("abcdefghijklmnopqrstuvwxyz"))
+    return ["".join(alpha[rng.integers(0, 26, int(n))]) for n in lens]
+
+
+def _length_stream_runs(metas, want_encoding):
+    """(sub-encoding, count) of every run in every stripe's v_s LENGTH
+    stream, walked from the files; asserts the column encoding."""
+    out = []
+    for m in metas:
+        fi = ol.parse_orc(m["path"])
+        cid = fi.column_names.index("v_s") + 1
+        with open(m["path"], "rb") as f:
+            raw = f.read()
+        for st in fi.stripes:
+            assert st.encodings[cid] == want_encoding
+            ln = ol.find_stream(st, cid, ol.STREAM_LENGTH)
+            out += S.run_headers(raw[ln.offset:ln.offset + ln.length])
+    return out
+
+
+class TestOrcStringLengthPatchedBase:
+    """LENGTH streams the writer encodes as PATCHED_BASE: mostly tiny
+    strings with a few long ones. The host LENGTH decoder once sized a
+    patch entry as round_up_8(8 * pgw + pw) bits where the spec packs it at
+    closest_fixed_bits(pgw + pw); such files then failed plan creation, or
+    could read wrong lengths."""
+
+    def test_direct_v2_outlier_lengths(self, tmp_path):
+        rng = np.random.default_rng(811)
+        runs = gen_runs_dedup(3, 4000, n_value_cols=1, seed=811,
+                              delete_frac=0.15)
+        strs = [_random_words(rng, _outlier_lengths(rng, len(r["key"])))
+                for r in runs]
+        metas = _write_orc_str(runs, strs, str(tmp_path), 0.0)
+        encs = [e for e, _ in _length_stream_runs(metas, ol.ENC_DIRECT_V2)]
+        assert encs.count(S.PATCHED_BASE) >= 1, "no PATCHED_BASE run written"
+        _read_and_compare(runs, strs, None, metas)
+
+    def test_dictionary_v2_outlier_lengths(self, tmp_path):
+        # the stripe dictionary's LENGTH stream (decoded until exhausted)
+        rng = np.random.default_rng(812)
+        runs = gen_runs_dedup(2, 9000, n_value_cols=1, seed=812,
+                              delete_frac=0.15)
+        vocab = sorted(set(_random_words(rng, _outlier_lengths(rng, 3300))))
+        vocab = np.array(vocab[:3000], dtype=object)
+        rng.shuffle(vocab)
+        strs = [vocab[rng.integers(0, len(vocab), len(r["key"]))].tolist()
+                for r in runs]
+        metas = _write_orc_str(runs, strs, str(tmp_path), 1.0)
+        encs = [e for e, _ in
+                _length_stream_runs(metas, ol.ENC_DICTIONARY_V2)]
+        assert encs.count(S.PATCHED_BASE) >= 1, "no PATCHED_BASE run written"
+        _read_and_compare(runs, strs, None, metas)
 
 
 class TestOrcStrings:
