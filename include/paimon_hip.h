@@ -245,6 +245,34 @@ int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
                            int kind, int out_esize, int mode,
                            int64_t src_shift, void *out, int64_t out_cap);
 
+/* Decode one ORC DECIMAL DATA stream (zigzag base-128 varints of the
+ * unscaled values) through the product's own decoder, so tests can force
+ * every value length, alignment and scale instead of taking what a file
+ * writer happens to pick.
+ *   scales: n_values per-value data scales (what the SECONDARY stream holds
+ *     once decoded), or NULL when every value already has the column scale.
+ *   precision, scale: the column's. precision 1..18 as a plan may declare,
+ *     or 19 = the whole int64 range (10^19 > 2^63), which lets a stream hold
+ *     the 10-byte values no decimal(p <= 18) column can.
+ *   mode 0, host (no GPU): the staging prescan plus the scalar core the
+ *     kernel shares (orc_decimal_core.h).
+ *   mode 2, device path: uploads the stream as staging does (16-byte tail
+ *     pad) at src_shift (0..7) bytes past an 8-byte-aligned device address,
+ *     prescans, launches k_orc_varint once over all units. The device output
+ *     sits between two 64-element guard zones and is pre-filled, like them,
+ *     with the byte 0xA5. Owns its device memory; needs no session.
+ * Writes n_values elements of out_esize (4 or 8) bytes to `out` (out_cap >=
+ * n_values elements) and returns n_values. Returns -1 with pmh_last_error()
+ * set on a malformed or truncated stream, a value the column cannot hold
+ * (data scale above the column scale or negative, magnitude of 10^precision
+ * or more, outside int32 at out_esize 4), bad arguments or a HIP error, and
+ * -2 when the kernel changed a guard zone (the output is still copied). */
+int64_t pmh_debug_orc_decimal(const void *data, int64_t len,
+                              const int32_t *scales, int precision,
+                              int scale, int64_t n_values, int out_esize,
+                              int mode, int64_t src_shift, void *out,
+                              int64_t out_cap);
+
 /* Parse one deletion vector from a DV index file slice (DeletionFile
  * {path, offset, length}; BitmapDeletionVector.java:98-112 wrapper around
  * the portable Roaring serialization). Writes up to `cap` deleted

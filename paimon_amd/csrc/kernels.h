@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "orc_decimal_core.h"
+
 namespace pmh {
 
 // Hard capacity limits (validated host-side at plan creation):
@@ -91,7 +93,9 @@ struct Rlev2Chunk {
     uint8_t patch_pgw;   // PATCHED: gap bits
     uint8_t patch_cfb;   // PATCHED: packed entry bits
     uint8_t dense_target;  // 0: contig (positioned); 1: dense buffer
-                           // (PRESENT scatter follows)
+                           // (PRESENT scatter follows); 2: the (run,
+                           // column)'s int32 decimal-scale scratch
+                           // (out_start = scratch index)
     uint8_t _pad[2];
     uint64_t out_addr;     // absolute output base (patched at finalize)
 };
@@ -201,6 +205,13 @@ hipError_t pmh_launch_zstd_pages(const uint8_t *src,
 
 hipError_t pmh_launch_rlev2(const Rlev2Chunk *chunks, int64_t n_chunks,
                             hipStream_t stream);
+
+// Decode ORC DECIMAL varint work units (VarintUnit, orc_decimal_core.h) into
+// a dense int32/int64 column of unscaled values at the column scale. One
+// wave per unit. Units that read a scale scratch must be launched after the
+// k_rlev2 launch that fills it, on the same stream.
+hipError_t pmh_launch_orc_varint(const VarintUnit *units, int64_t n_units,
+                                 hipStream_t stream);
 
 hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
                                 int64_t tile_rows, int64_t n_bounds,

@@ -3096,6 +3096,116 @@ __global__ void k_rlev2(const Rlev2Chunk *chunks, int64_t n_chunks) {
 }
 
 
+// --------------------------------------------------------- k_orc_varint
+//
+// ORC DECIMAL DATA decode: zigzag base-128 varints, one per non-null row
+// (orc_decimal_core.h). Varints carry no run headers, so the host prescan
+// only cuts the stream every 512 values; finding the value boundaries is
+// the kernel's work. One 64-lane wave per unit, no workgroup barrier:
+//  (a) lanes sweep the unit's bytes with aligned 8-byte loads; a byte ends a
+//      value when its high bit is clear, so ~word & 0x80.. is a terminator
+//      mask. A wave prefix count numbers the terminators and each value's
+//      END offset lands in the wave's LDS table (<= 512 x 2 bytes; a unit
+//      is <= 5120 bytes, so offsets fit 16 bits);
+//  (b) one lane per value reads its span (end[j-1], end[j]] as up to three
+//      aligned words, then runs the shared scalar core: compact, zigzag,
+//      rescale to the column scale, range check.
+// The table is written and read by the same wave only: LDS operations of
+// one wave execute in order, __threadfence_block() keeps the compiler from
+// moving the reads up and waits out the writes.
+// Loads may touch up to 7 bytes before the unit (same upload) and the
+// 16-byte tail pad behind the stream; stores stay in [out_start, +count).
+__launch_bounds__(256) __global__
+void k_orc_varint(const VarintUnit *units, int64_t n_units) {
+    __shared__ uint16_t s_end[4][ODC_UNIT_VALUES];
+    const int wave = (int)(threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63);
+    const int waves = (int)(blockDim.x >> 6);
+    uint16_t *ends = s_end[wave];
+    for (int64_t uidx = (int64_t)blockIdx.x * waves + wave; uidx < n_units;
+         uidx += (int64_t)gridDim.x * waves) {
+        const VarintUnit u = units[uidx];
+        const uint64_t base = u.src & ~7ull;     // absolute 8-byte alignment
+        const int lead = (int)(u.src - base);    // 0..7 bytes before the unit
+        const int span = lead + u.nbytes;        // bytes from base
+        const int n_words = (span + 7) >> 3;
+        // ---- (a) terminator sweep
+        int running = 0;  // terminators in earlier rounds (wave-uniform)
+        for (int w0 = 0; w0 < n_words; w0 += 64) {
+            const int w = w0 + lane;
+            uint64_t term = 0;
+            if (w < n_words) {
+                const uint64_t word =
+                    *reinterpret_cast<const uint64_t *>(base + (uint64_t)w * 8);
+                term = ~word & 0x8080808080808080ull;
+                // drop bytes outside [lead, span)
+                const int lo = lead - w * 8;  // first valid byte of the word
+                if (lo > 0) term &= ~0ull << (lo * 8);
+                const int hi = span - w * 8;  // bytes of the word in the unit
+                if (hi < 8) term &= (1ull << (hi * 8)) - 1;
+            }
+            const int cnt = __popcll(term);
+            int incl = cnt;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += up;
+            }
+            int idx = running + incl - cnt;  // index of this lane's first
+            while (term) {
+                const int byte = (__ffsll((long long)term) - 1) >> 3;
+                term &= term - 1;
+                if (idx < ODC_UNIT_VALUES)
+                    ends[idx] = (uint16_t)(w * 8 + byte - lead);
+                idx++;
+            }
+            running += __shfl(incl, 63, 64);
+        }
+        __threadfence_block();
+        // ---- (b) one lane per value
+        // a unit the prescan cut holds exactly `count` terminators; fewer
+        // would leave table slots unwritten, so they are not read
+        const int n_vals = running < u.count ? running : u.count;
+        uint32_t errs =
+            running < u.count ? (1u << (ODC_ERR_SHIFT + ODC_ERR_WIDTH)) : 0;
+        const int32_t *scales = (const int32_t *)u.scale_addr;
+        void *out = (void *)u.out_addr;
+        for (int j = lane; j < n_vals; j += 64) {
+            const int start = j ? (int)ends[j - 1] + 1 : 0;
+            int len = (int)ends[j] - start + 1;
+            int err = ODC_OK;
+            if (len > ODC_MAX_VARINT) {  // prescan refuses these
+                len = ODC_MAX_VARINT;
+                err = ODC_ERR_WIDTH;
+            }
+            const uint64_t a = u.src + (uint64_t)start;
+            const uint64_t ab = a & ~7ull;
+            const int sh = (int)(a - ab) * 8;  // 0..56
+            const int reach = (int)(a - ab) + len;  // bytes from ab
+            uint64_t w0 = *reinterpret_cast<const uint64_t *>(ab);
+            uint64_t w1 = 0, w2 = 0;
+            if (reach > 8) w1 = *reinterpret_cast<const uint64_t *>(ab + 8);
+            if (reach > 16) w2 = *reinterpret_cast<const uint64_t *>(ab + 16);
+            uint64_t b0 = w0, b1 = w1;
+            if (sh) {
+                b0 = (w0 >> sh) | (w1 << (64 - sh));
+                b1 = (w1 >> sh) | (w2 << (64 - sh));
+            }
+            const uint64_t raw = odc_compact(b0, b1, len, &err);
+            int64_t r = 0;
+            if (!err) {
+                const int ds = scales ? scales[j] : u.scale;
+                err = odc_rescale(zz_dec(raw), ds, u.precision, u.scale,
+                                  u.out_esize, &r);
+            }
+            if (err) errs |= 1u << (ODC_ERR_SHIFT + err);
+            dense_store(out, u.out_esize, u.out_start + j, r);
+        }
+        if (errs && u.err_addr) atomicOr((uint32_t *)u.err_addr, errs);
+        // the next unit's sweep overwrites the table: reads must be done
+        __threadfence_block();
+    }
+}
+
 // ------------------------------------------------------------ DELTA decode
 //
 // Parquet DELTA_BINARY_PACKED (VectorizedDeltaBinaryPackedReader.java /
@@ -4363,6 +4473,16 @@ hipError_t pmh_launch_rlev2(const Rlev2Chunk *chunks, int64_t n_chunks,
     return hipGetLastError();
 }
 
+
+hipError_t pmh_launch_orc_varint(const VarintUnit *units, int64_t n_units,
+                                 hipStream_t stream) {
+    int waves_per_block = 4;  // 256 threads
+    int64_t want = (n_units + waves_per_block - 1) / waves_per_block;
+    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    hipLaunchKernelGGL(k_orc_varint, dim3(blocks), dim3(256), 0, stream,
+                       units, n_units);
+    return hipGetLastError();
+}
 
 hipError_t pmh_launch_delta_sum(const DeltaChunk *chunks, int64_t n_chunks,
                                 int64_t *sums, hipStream_t stream) {

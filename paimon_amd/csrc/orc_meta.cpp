@@ -154,6 +154,8 @@ OrcFileMeta parse_orc_meta(const uint8_t *data, int64_t size) {
                 return out;
             }
             out.column_kinds.push_back((int)pb_int(types[sub], 1));
+            out.column_precisions.push_back((int)pb_int(types[sub], 5));
+            out.column_scales.push_back((int)pb_int(types[sub], 6));
         }
         // stripes (field 3)
         auto sit = footer.find(3);

@@ -4,7 +4,8 @@
 // (format/orc/OrcReaderFactory.java:108-171 + vendored
 // org.apache.orc.impl.RecordReaderImpl overrides). Decode arithmetic
 // (RLEv2 / byte-RLE / boolean-RLE) runs on the GPU (kernels.hip); this
-// parser only locates streams. Uncompressed ORC only (v1).
+// parser only locates streams; compressed files (zlib / snappy / zstd)
+// have their footers inflated here and their streams at staging.
 #pragma once
 
 #include <cstdint>
@@ -23,6 +24,7 @@ enum OrcTypeKind {
     ORC_DOUBLE = 6,
     ORC_STRING = 7,
     ORC_STRUCT = 12,
+    ORC_DECIMAL = 14,
 };
 
 enum OrcStreamKind {
@@ -30,6 +32,7 @@ enum OrcStreamKind {
     ORC_STREAM_DATA = 1,
     ORC_STREAM_LENGTH = 2,
     ORC_STREAM_DICTIONARY = 3,
+    ORC_STREAM_SECONDARY = 5,  // decimal: per-value scale, signed RLEv2
 };
 
 struct OrcStream {
@@ -55,6 +58,9 @@ struct OrcFileMeta {
     int64_t compression_block_size = 0;
     std::vector<std::string> column_names;  // flat struct; col id = idx + 1
     std::vector<int> column_kinds;
+    // Type.precision / Type.scale (DECIMAL columns; 0 elsewhere)
+    std::vector<int> column_precisions;
+    std::vector<int> column_scales;
     std::vector<OrcStripe> stripes;
     std::string error;
     bool ok() const { return error.empty(); }

@@ -561,6 +561,14 @@ struct RunCol {
     bool orc_encoded = false;
     std::vector<Rlev2Chunk> rlev2_host;
     Rlev2Chunk *rlev2_dev = nullptr;
+    // ORC DECIMAL: varint work units (k_orc_varint). scale_dev is the
+    // (run, column)'s int32 data-scale scratch: stripes whose SECONDARY
+    // stream is not uniformly the column scale append their scales to it
+    // (scale_rows so far). Units of such stripes carry 1 + the scratch index
+    // of their first value in scale_addr until finalize patches the address
+    std::vector<VarintUnit> varint_host;
+    int64_t scale_rows = 0;
+    int32_t *scale_dev = nullptr;
     // parquet DELTA_BINARY_PACKED pages (decoded on GPU at read time)
     std::vector<DeltaChunk> delta_host;
     std::vector<DeltaStream> dstreams_host;
@@ -636,6 +644,8 @@ struct Section {
     // batched decode work (all run-columns in ONE launch each)
     Rlev2Chunk *rlev2_all = nullptr;
     int64_t n_rlev2 = 0;
+    VarintUnit *varint_all = nullptr;
+    int64_t n_varint = 0;
     DeltaChunk *delta_all = nullptr;
     int64_t n_delta = 0;
     DeltaStream *dstreams_all = nullptr;
@@ -1557,6 +1567,20 @@ static bool prescan_present(const uint8_t *s, int64_t len, int64_t n_rows,
     return true;
 }
 
+// Message for the ORC decimal bits of a section's device error word
+// (k_orc_varint ORs 1 << (ODC_ERR_SHIFT + ODC_ERR_*)).
+static std::string orc_decimal_error(uint32_t err_word) {
+    std::string m = "ORC decimal rescale failed:";
+    const char *sep = " ";
+    for (int code = 1; code <= ODC_ERR_WIDTH; code++)
+        if (err_word & (1u << (ODC_ERR_SHIFT + code))) {
+            m += sep;
+            m += odc_err_text(code);
+            sep = "; ";
+        }
+    return m;
+}
+
 // Stage one ORC file's stripes for the required columns.
 static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                            const StagedFile &sf, Run &run, int64_t row_base) {
@@ -1584,6 +1608,39 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                           fd.path.c_str(), cols[c].name.c_str(), ckind);
                 return false;
             }
+            if (ckind == ORC_DECIMAL || cols[c].precision > 0) {
+                // decimals ride as unscaled INT32/INT64 at the DECLARED
+                // (precision, scale): the file must say the same
+                const int fp = om.column_precisions[cid - 1];
+                const int fs = om.column_scales[cid - 1];
+                if (ckind != ORC_DECIMAL) {
+                    set_error("%s col %s: declared decimal(%d,%d) but ORC "
+                              "kind is %d, not DECIMAL", fd.path.c_str(),
+                              cols[c].name.c_str(), cols[c].precision,
+                              cols[c].scale, ckind);
+                    return false;
+                }
+                if (cols[c].precision <= 0) {
+                    set_error("%s col %s: ORC DECIMAL(%d,%d) column read as "
+                              "non-decimal type", fd.path.c_str(),
+                              cols[c].name.c_str(), fp, fs);
+                    return false;
+                }
+                if (fp > 18) {
+                    set_error("%s col %s: ORC DECIMAL precision %d above 18 "
+                              "is not supported (unscaled values ride as "
+                              "INT32/INT64)", fd.path.c_str(),
+                              cols[c].name.c_str(), fp);
+                    return false;
+                }
+                if (fp != cols[c].precision || fs != cols[c].scale) {
+                    set_error("%s col %s: declared decimal(%d,%d) but the "
+                              "ORC file holds decimal(%d,%d)",
+                              fd.path.c_str(), cols[c].name.c_str(),
+                              cols[c].precision, cols[c].scale, fp, fs);
+                    return false;
+                }
+            }
             const int stored = cols[c].stored_esize;
             const OrcStream *data = orc_find_stream(st, cid, ORC_STREAM_DATA);
             const OrcStream *present =
@@ -1603,6 +1660,22 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                           "DICTIONARY_V2)",
                           fd.path.c_str(), cols[c].name.c_str(), cenc);
                 return false;
+            }
+            const OrcStream *secondary = nullptr;
+            if (ckind == ORC_DECIMAL) {
+                if (cenc != 2) {
+                    set_error("%s col %s: ORC DECIMAL column encoding %d not "
+                              "supported (DIRECT_V2 only; RLEv1 scales are "
+                              "out of scope)", fd.path.c_str(),
+                              cols[c].name.c_str(), cenc);
+                    return false;
+                }
+                secondary = orc_find_stream(st, cid, ORC_STREAM_SECONDARY);
+                if (!secondary) {
+                    set_error("%s col %s: SECONDARY stream missing",
+                              fd.path.c_str(), cols[c].name.c_str());
+                    return false;
+                }
             }
             // compressed streams decompress on the host at staging, like
             // the parquet zstd path (on-GPU codecs: §8f); the RLEv2/byte-RLE
@@ -1858,7 +1931,87 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                 dense_target = 1;
             }
             bool ok;
-            if (ckind == ORC_BYTE) {
+            if (ckind == ORC_DECIMAL) {
+                const uint8_t *sec_ptr = sf.data.data() + secondary->offset;
+                int64_t sec_len = secondary->length;
+                std::vector<uint8_t> sec_dec;
+                if (om.compression != 0) {
+                    std::string cerr;
+                    if (!orc_decompress(sec_ptr, sec_len, om.compression,
+                                        om.compression_block_size, sec_dec,
+                                        cerr)) {
+                        set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
+                                  cols[c].name.c_str(), cerr.c_str());
+                        return false;
+                    }
+                    sec_ptr = sec_dec.data();
+                    sec_len = (int64_t)sec_dec.size();
+                }
+                // SECONDARY: signed RLEv2 data scales. Constant runs equal
+                // to the column scale (what the common writers emit) need
+                // no device work at all; anything else decodes through
+                // k_rlev2 into the (run, column) scale scratch
+                std::vector<Rlev2Chunk> sch;
+                const int64_t sc0 = rc.scale_rows;
+                if (!prescan_rlev2(sec_ptr, sec_len, n_dense, 1, 4, 2, 0,
+                                   sc0, sch)) {
+                    set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
+                              cols[c].name.c_str(),
+                              std::string(last_error()).c_str());
+                    return false;
+                }
+                bool uniform = true;
+                int64_t sc_end = sc0;
+                for (const auto &k : sch) {
+                    const bool constant =
+                        k.kind == 0 ||
+                        (k.kind == 3 && k.width == 0 && k.delta == 0);
+                    if (!constant || k.base != cols[c].scale) uniform = false;
+                    sc_end = k.out_start + k.count;
+                }
+                if (!uniform) {
+                    // the scratch is sized by the value count: a stream
+                    // whose last run decodes past it is refused
+                    if (sc_end != sc0 + n_dense) {
+                        set_error("%s col %s: SECONDARY stream holds %lld "
+                                  "scales for %lld values", fd.path.c_str(),
+                                  cols[c].name.c_str(),
+                                  (long long)(sc_end - sc0),
+                                  (long long)n_dense);
+                        return false;
+                    }
+                    void *sdev = plan->bufs.alloc(sec_len + 16);
+                    if (!sdev) return false;
+                    if (hipMemcpy(sdev, sec_ptr, sec_len,
+                                  hipMemcpyHostToDevice) != hipSuccess) {
+                        set_error("H2D failed");
+                        return false;
+                    }
+                    plan->encoded_bytes_total += sec_len;
+                    for (auto &k : sch) {
+                        k.src += (uint64_t)sdev;
+                        if (k.kind == 2) k.patch_src += (uint64_t)sdev;
+                    }
+                    rc.rlev2_host.insert(rc.rlev2_host.end(), sch.begin(),
+                                         sch.end());
+                    rc.scale_rows += n_dense;
+                }
+                const char *why = "";
+                const size_t u0 = rc.varint_host.size();
+                ok = prescan_varint(data_ptr, data_len, n_dense, stored,
+                                    cols[c].precision, cols[c].scale,
+                                    dense_target, (uint64_t)dev, dense0,
+                                    rc.varint_host, &why);
+                if (!ok)
+                    set_error("%s col %s: %s", fd.path.c_str(),
+                              cols[c].name.c_str(), why);
+                else if (!uniform)
+                    for (size_t i = u0; i < rc.varint_host.size(); i++) {
+                        VarintUnit &vu = rc.varint_host[i];
+                        vu.scale_addr =
+                            (uint64_t)(1 + sc0 + (vu.out_start - dense0));
+                    }
+            } else if (ckind == ORC_BYTE) {
                 ok = prescan_byterle(data_ptr, data_len, n_dense, stored,
                                      dense_target, (uint64_t)dev, dense0,
                                      rc.rlev2_host);
@@ -2718,9 +2871,22 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
             rc.levels_host.clear();
             rc.levels_host.shrink_to_fit();
         }
+        if (rc.scale_rows) {
+            rc.scale_dev =
+                (int32_t *)plan->bufs.alloc((size_t)rc.scale_rows * 4);
+            if (!rc.scale_dev) return false;
+        }
         for (auto &vc : rc.rlev2_host)
-            vc.out_addr =
-                vc.dense_target ? (uint64_t)rc.dense_dev : (uint64_t)rc.contig;
+            vc.out_addr = vc.dense_target == 2 ? (uint64_t)rc.scale_dev
+                          : vc.dense_target    ? (uint64_t)rc.dense_dev
+                                               : (uint64_t)rc.contig;
+        for (auto &vu : rc.varint_host) {
+            vu.out_addr =
+                vu.dense_target ? (uint64_t)rc.dense_dev : (uint64_t)rc.contig;
+            if (vu.scale_addr)
+                vu.scale_addr =
+                    (uint64_t)(rc.scale_dev + (vu.scale_addr - 1));
+        }
         DevPage dp{(uint64_t)rc.contig, 0};
         rc.pages_host.assign(1, dp);
         rc.n_pages = 1;
@@ -3071,6 +3237,7 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
         return d;
     };
     std::vector<Rlev2Chunk> all_v;
+    std::vector<VarintUnit> all_u;
     std::vector<RleChunk> all_d;
     std::vector<DeltaChunk> all_dc;
     std::vector<DeltaStream> all_ds;
@@ -3079,10 +3246,13 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
             sec.any_dict |= rc.dict_encoded;
             sec.any_decode |= rc.dict_encoded || rc.has_nulls ||
                               !rc.rlev2_host.empty() ||
+                              !rc.varint_host.empty() ||
                               !rc.delta_host.empty() ||
                               !rc.gathers.empty();
             all_v.insert(all_v.end(), rc.rlev2_host.begin(),
                          rc.rlev2_host.end());
+            all_u.insert(all_u.end(), rc.varint_host.begin(),
+                         rc.varint_host.end());
             all_d.insert(all_d.end(), rc.def_host.begin(), rc.def_host.end());
             const int64_t cbase = (int64_t)all_dc.size();
             all_dc.insert(all_dc.end(), rc.delta_host.begin(),
@@ -3099,6 +3269,20 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
         sec.rlev2_all =
             (Rlev2Chunk *)up(all_v.data(), all_v.size() * sizeof(Rlev2Chunk));
         if (!sec.rlev2_all) return false;
+    }
+    sec.n_varint = (int64_t)all_u.size();
+    if (sec.n_varint) {
+        // decimal range / scale violations land in the section's error word
+        // (the lookup section owns none yet)
+        if (!sec.err_dev) {
+            sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
+            if (!sec.err_dev || hipMemset(sec.err_dev, 0, 4) != hipSuccess)
+                return false;
+        }
+        for (auto &vu : all_u) vu.err_addr = (uint64_t)sec.err_dev;
+        sec.varint_all =
+            (VarintUnit *)up(all_u.data(), all_u.size() * sizeof(VarintUnit));
+        if (!sec.varint_all) return false;
     }
     if (sec.n_def) {
         sec.def_all =
@@ -3131,6 +3315,16 @@ static hipError_t launch_section_decode(pmh_plan_t *p, Section &sec,
             hipError_t e = pmh_launch_rlev2(sec.rlev2_all, sec.n_rlev2, st);
             if (e != hipSuccess) {
                 *what = "rlev2";
+                return e;
+            }
+        }
+        if (sec.n_varint) {
+            // after k_rlev2 on the same stream: units with per-value scales
+            // read the scratch it fills
+            hipError_t e =
+                pmh_launch_orc_varint(sec.varint_all, sec.n_varint, st);
+            if (e != hipSuccess) {
+                *what = "orc_varint";
                 return e;
             }
         }
@@ -3732,6 +3926,19 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                           hipGetErrorString(de));
                 return nullptr;
             }
+            if (ls.n_varint) {
+                uint32_t ew = 0;
+                if (hipMemcpy(&ew, ls.err_dev, 4, hipMemcpyDeviceToHost) !=
+                    hipSuccess) {
+                    set_error("lookup levels: err D2H failed");
+                    return nullptr;
+                }
+                if (ew >> ODC_ERR_SHIFT) {
+                    set_error("lookup levels: %s",
+                              orc_decimal_error(ew).c_str());
+                    return nullptr;
+                }
+            }
         }
         for (auto &sec_files : sections) {
             Section sec;
@@ -4301,6 +4508,10 @@ collect:
                   "predecessor tile");
         return -1;
     }
+    if (err_word >> ODC_ERR_SHIFT) {
+        set_error("%s", orc_decimal_error(err_word).c_str());
+        return -1;
+    }
     if (err_word & 8) {
         set_error("Top level key-value already exists (two runs at "
                   "max_level hold the same key; "
@@ -4661,6 +4872,140 @@ int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
     if (d_src) (void)hipFree(d_src);
     if (d_out) (void)hipFree(d_out);
     if (d_chunks) (void)hipFree(d_chunks);
+    return rc;
+}
+
+// Stream-level entry to the ORC DECIMAL decode (prescan_varint, the shared
+// scalar core, k_orc_varint): see paimon_hip.h. Calls the very functions the
+// plan calls.
+int64_t pmh_debug_orc_decimal(const void *data, int64_t len,
+                              const int32_t *scales, int precision,
+                              int scale, int64_t n_values, int out_esize,
+                              int mode, int64_t src_shift, void *out,
+                              int64_t out_cap) {
+    const uint8_t *s = (const uint8_t *)data;
+    if ((!s && len > 0) || len < 0 || n_values < 0 ||
+        (mode != 0 && mode != 2) || (out_esize != 4 && out_esize != 8) ||
+        precision < 1 || precision > ODC_MAX_PRECISION || scale < 0 ||
+        scale > 18 || src_shift < 0 || src_shift > 7 || out_cap < n_values ||
+        (n_values > 0 && !out)) {
+        set_error("pmh_debug_orc_decimal: bad arguments (mode 0|2, out_esize "
+                  "4|8, precision 1..19, scale 0..18, src_shift 0..7, "
+                  "out_cap >= n_values >= 0)");
+        return -1;
+    }
+    if (n_values == 0) return 0;
+    std::vector<VarintUnit> units;
+    const char *why = "";
+    if (mode == 0) {  // host twin
+        if (!prescan_varint(s, len, n_values, out_esize, precision, scale, 0,
+                            0, 0, units, &why)) {
+            set_error("pmh_debug_orc_decimal: %s", why);
+            return -1;
+        }
+        for (const auto &u : units) {
+            int bad = 0;
+            int err = odc_decode_unit_host(
+                s + u.src, u, scales ? scales + u.out_start : nullptr, out,
+                &bad);
+            if (err) {
+                set_error("pmh_debug_orc_decimal: ORC decimal rescale "
+                          "failed at value %lld: %s",
+                          (long long)(u.out_start + bad), odc_err_text(err));
+                return -1;
+            }
+        }
+        return n_values;
+    }
+    // device path: stream at an 8-byte-aligned address + src_shift with the
+    // 16-byte tail pad staging gives it; output between two guard zones
+    const int64_t GUARD = 64;  // elements, each side
+    const uint8_t FILL = 0xA5;
+    uint8_t *d_src = nullptr, *d_out = nullptr;
+    int32_t *d_scales = nullptr;
+    uint32_t *d_err = nullptr;
+    VarintUnit *d_units = nullptr;
+    const size_t out_bytes = (size_t)(n_values + 2 * GUARD) * out_esize;
+    std::vector<uint8_t> back(out_bytes);
+    int64_t rc = -1;
+    do {
+        if (hipMalloc(&d_src, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMalloc(&d_out, out_bytes) != hipSuccess ||
+            hipMalloc(&d_err, 4) != hipSuccess ||
+            (scales &&
+             hipMalloc(&d_scales, (size_t)n_values * 4) != hipSuccess)) {
+            set_error("pmh_debug_orc_decimal: hipMalloc failed");
+            break;
+        }
+        if (((uint64_t)d_src & 7) != 0) {
+            set_error("pmh_debug_orc_decimal: device allocation not "
+                      "8-aligned");
+            break;
+        }
+        if (hipMemset(d_src, 0, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMemset(d_out, FILL, out_bytes) != hipSuccess ||
+            hipMemset(d_err, 0, 4) != hipSuccess ||
+            (len && hipMemcpy(d_src + src_shift, s, (size_t)len,
+                              hipMemcpyHostToDevice) != hipSuccess) ||
+            (scales && hipMemcpy(d_scales, scales, (size_t)n_values * 4,
+                                 hipMemcpyHostToDevice) != hipSuccess)) {
+            set_error("pmh_debug_orc_decimal: H2D failed");
+            break;
+        }
+        if (!prescan_varint(s, len, n_values, out_esize, precision, scale, 0,
+                            (uint64_t)(d_src + src_shift), 0, units, &why)) {
+            set_error("pmh_debug_orc_decimal: %s", why);
+            break;
+        }
+        for (auto &u : units) {
+            u.out_addr = (uint64_t)(d_out + GUARD * out_esize);
+            u.scale_addr =
+                d_scales ? (uint64_t)(d_scales + u.out_start) : 0;
+            u.err_addr = (uint64_t)d_err;
+        }
+        if (hipMalloc(&d_units, units.size() * sizeof(VarintUnit)) !=
+                hipSuccess ||
+            hipMemcpy(d_units, units.data(),
+                      units.size() * sizeof(VarintUnit),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("pmh_debug_orc_decimal: unit upload failed");
+            break;
+        }
+        uint32_t err_word = 0;
+        hipError_t e =
+            pmh_launch_orc_varint(d_units, (int64_t)units.size(), nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess)
+            e = hipMemcpy(back.data(), d_out, out_bytes,
+                          hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(&err_word, d_err, 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_error("pmh_debug_orc_decimal: k_orc_varint: %s",
+                      hipGetErrorString(e));
+            break;
+        }
+        rc = n_values;
+        const size_t g = (size_t)GUARD * out_esize;
+        for (size_t i = 0; i < g; i++)
+            if (back[i] != FILL || back[out_bytes - 1 - i] != FILL) {
+                set_error("pmh_debug_orc_decimal: k_orc_varint wrote "
+                          "outside its output (guard zone changed)");
+                rc = -2;
+                break;
+            }
+        memcpy(out, back.data() + g, (size_t)n_values * out_esize);
+        if (rc >= 0 && (err_word >> ODC_ERR_SHIFT)) {
+            set_error("pmh_debug_orc_decimal: %s",
+                      orc_decimal_error(err_word).c_str());
+            rc = -1;
+        }
+    } while (0);
+    if (d_src) (void)hipFree(d_src);
+    if (d_out) (void)hipFree(d_out);
+    if (d_scales) (void)hipFree(d_scales);
+    if (d_err) (void)hipFree(d_err);
+    if (d_units) (void)hipFree(d_units);
     return rc;
 }
 

@@ -324,6 +324,45 @@ def debug_orc_ints(stream, n_values, kind, mode, out_esize=8, src_shift=0):
     return out[:n_values]
 
 
+ORC_DECIMAL_HOST, ORC_DECIMAL_DEVICE = 0, 2
+ORC_DECIMAL_FULL_RANGE = 19  # precision: the whole int64 range
+
+
+def debug_orc_decimal(data, n_values, precision, scale, mode, scales=None,
+                      out_esize=8, src_shift=0):
+    """One ORC DECIMAL DATA stream (zigzag varints) through the product's
+    decoder (pmh_debug_orc_decimal). scales: per-value data scales, None =
+    all at the column scale. ORC_DECIMAL_HOST runs the prescan and the
+    scalar core on the host; ORC_DECIMAL_DEVICE returns what k_orc_varint
+    wrote (needs a GPU). Returns unscaled values at the column scale as
+    int32/int64 by out_esize. Raises RuntimeError on a rejected stream or
+    value; a device store outside the output raises AssertionError."""
+    lib = load_lib()
+    lib.pmh_debug_orc_decimal.restype = ctypes.c_int64
+    lib.pmh_debug_orc_decimal.argtypes = [
+        ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+    data = bytes(data)
+    sc = None
+    if scales is not None:
+        sc = np.ascontiguousarray(scales, dtype=np.int32)
+        if len(sc) != n_values:
+            raise ValueError("scales must hold n_values entries")
+    out = np.empty(max(n_values, 1),
+                   dtype=np.int32 if out_esize == 4 else np.int64)
+    n = lib.pmh_debug_orc_decimal(
+        data, len(data),
+        sc.ctypes.data_as(ctypes.c_void_p) if sc is not None else None,
+        precision, scale, n_values, out_esize, mode, src_shift,
+        out.ctypes.data_as(ctypes.c_void_p), len(out))
+    if n == -2:
+        raise AssertionError(last_error())
+    if n < 0:
+        raise RuntimeError(last_error())
+    return out[:n_values]
+
+
 def interval_partition(min_keys, max_keys):
     """Returns (section_id, run_id) per input file, per the IntervalPartition
     restatement in libpaimon_hip (plan.cpp)."""
