@@ -63,6 +63,42 @@ enum pmh_dtype {
      * separate dtype: p <= 9 rides INT32, p <= 18 INT64 (unscaled values,
      * ParquetSchemaConverter.java:153-171) with precision/scale set. */
     PMH_DT_STRING = 7,
+    /* BOOLEAN (parquet BOOLEAN / ORC BOOLEAN, ParquetSchemaConverter.java:
+     * 126-216, OrcTypeUtil.java:67-114): one byte per row, 0 or 1. */
+    PMH_DT_BOOL = 8,
+};
+
+/* Logical annotation of an INT32/INT64 column (pmh_col.logical). DATE, TIME
+ * and TIMESTAMP are not separate dtypes: like DECIMAL they ride the integer
+ * the file stores (ParquetSchemaConverter.java:126-216, 306-323;
+ * OrcTypeUtil.java:67-114) and the batch carries the annotation:
+ *   date                      INT32 days since 1970-01-01
+ *                             (parquet INT32 DATE / ORC DATE)
+ *   time                      INT32 milliseconds of the day
+ *                             (parquet INT32 TIME MILLIS / ORC INT)
+ *   timestamp(p <= 3) [_ltz]  INT64 milliseconds since the epoch
+ *   timestamp(4..6)   [_ltz]  INT64 microseconds since the epoch
+ *                             (parquet INT64 TIMESTAMP MILLIS|MICROS, ORC
+ *                             TIMESTAMP / TIMESTAMP_INSTANT for _ltz)
+ * A bare "timestamp" is timestamp(6). Values are handed out as the plain
+ * integers, filter literals are those integers (0/1 for booleans), and
+ * sequence_fields may name such a column. Limits (plan creation or the read
+ * fails, by name): key columns of these types and of boolean; precision
+ * above 6 (parquet INT96, sub-microsecond ORC); a parquet file whose
+ * physical type, annotation or timestamp unit differs from the declared
+ * type's; RLE-encoded parquet booleans (data page v2); RLEv1 (DIRECT) ORC
+ * timestamps; an ORC TIMESTAMP writer timezone other than UTC / GMT; ORC
+ * timestamps before 1970 with a fractional second, with nanos of 10^9 or
+ * more, or outside int64 in the column unit; numeric aggregators (sum, ...)
+ * over these types. */
+enum pmh_logical {
+    PMH_LT_NONE = 0,
+    PMH_LT_DATE = 1,
+    PMH_LT_TIME_MILLIS = 2,
+    PMH_LT_TIMESTAMP_MILLIS = 3,
+    PMH_LT_TIMESTAMP_MICROS = 4,
+    PMH_LT_TIMESTAMP_LTZ_MILLIS = 5,
+    PMH_LT_TIMESTAMP_LTZ_MICROS = 6,
 };
 
 typedef struct pmh_col {
@@ -81,6 +117,8 @@ typedef struct pmh_col {
     /* DECIMAL annotation on INT32/INT64 columns (0 = plain integer). */
     int32_t precision;
     int32_t scale;
+    /* enum pmh_logical on INT32/INT64 columns (0 = none). */
+    int32_t logical;
 } pmh_col;
 
 typedef struct pmh_batch {
@@ -117,6 +155,9 @@ void pmh_close_session(pmh_session_t *s);
  * {
  *   "key_cols":   [{"name": "_KEY_k", "type": "int64"}],
  *   "value_cols": [{"name": "v_k", "type": "int64"}, ...],   // read type
+ *       // types: tinyint..bigint, float, double, string, decimal(p,s),
+ *       // boolean, date, time, timestamp(p), timestamp_ltz(p) (enum
+ *       // pmh_logical says how the last four ride integers)
  *   "merge_engine": "deduplicate" | "partial-update",
  *   "drop_delete": true,         // !forceKeepDelete
  *   "ignore_delete": false,      // CoreOptions.IGNORE_DELETE
@@ -180,12 +221,25 @@ const char *pmh_last_error(void);
 char *pmh_debug_footer_json(const char *path);
 void pmh_free_string(char *s);
 
+/* Check one column of a data file against a declared plan type ("boolean",
+ * "date", "time", "timestamp(3)", ...) the way staging does, without a plan
+ * or a GPU: Parquet physical type, DATE / TIME / TIMESTAMP annotation and
+ * unit, boolean page encodings; ORC type kind and, for TIMESTAMP, each
+ * stripe's writer timezone. Returns 0, or -1 with pmh_last_error() set to
+ * the text plan creation would fail with. */
+int pmh_debug_check_column(const char *path, const char *column,
+                           const char *type);
+
 /* Write a Parquet v1 data file (PLAIN pages) from HOST columnar
  * buffers — the compaction write-back half of the CompactRewriter surface
  * (what KeyValueDataFileWriter + the vendored parquet-mr writer do in the
  * reference, io/KeyValueDataFileWriter.java:121-170). cols[i].data/valid
  * are host pointers at the column's output width (TINYINT/SMALLINT widen to
- * the INT32 physical type on write, matching the read path). No GPU
+ * the INT32 physical type on write, matching the read path). PMH_DT_BOOL
+ * columns (one 0/1 byte per row) are written as BOOLEAN, PLAIN, bit-packed
+ * LSB first; cols[i].logical on INT32/INT64 columns writes the DATE /
+ * TIME(MILLIS) / TIMESTAMP(MILLIS|MICROS) annotation as both converted_type
+ * and logicalType, isAdjustedToUTC set for the _LTZ values. No GPU
  * required. row_group_rows/page_rows <= 0 pick defaults (1M / 64k).
  * compression: NULL or "NONE" for uncompressed, "zstd" for ZSTD pages.
  * Returns 0, or -1 with pmh_last_error() set. */
@@ -272,6 +326,54 @@ int64_t pmh_debug_orc_decimal(const void *data, int64_t len,
                               int scale, int64_t n_values, int out_esize,
                               int mode, int64_t src_shift, void *out,
                               int64_t out_cap);
+
+/* Expand one BOOLEAN value stream through the product's own decoder
+ * (bits_core.h, k_bits_expand), so tests can force every unit shape and
+ * alignment instead of taking what a file writer happens to pick.
+ *   format 0: raw literal bits, as a Parquet PLAIN page payload holds them
+ *     (bit_order 0 = LSB first is Parquet's; 1 = MSB first is accepted too);
+ *     format 1: ORC boolean byte-RLE (runs and literal groups; bit_order 1 =
+ *     MSB first is ORC's).
+ *   out_esize: 1 (one byte per value) or 4 (the staged column width).
+ *   out_shift 0..7: the output starts this many ELEMENTS past an address
+ *     aligned to 8 elements, so the unit edges fall on every residue.
+ *   mode 0, host (no GPU): the staging prescan plus the scalar core the
+ *     kernel shares, over the same group geometry.
+ *   mode 2, device path: uploads the stream as staging does (16-byte tail
+ *     pad) at src_shift (0..7) bytes past an 8-byte-aligned device address,
+ *     prescans, launches k_bits_expand once over all units. The device
+ *     output sits between two 64-element guard zones and is pre-filled,
+ *     like them, with the byte 0xA5. Owns its device memory; needs no
+ *     session.
+ * Writes n_values elements of out_esize bytes to `out` (out_cap >= n_values
+ * elements) and returns n_values. Returns -1 with pmh_last_error() set on a
+ * truncated stream, bad arguments or a HIP error, and -2 when the kernel
+ * changed a guard zone (the output is still copied). */
+int64_t pmh_debug_bits(const void *stream, int64_t len, int64_t n_values,
+                       int bit_order, int format, int out_esize, int mode,
+                       int64_t src_shift, int64_t out_shift, void *out,
+                       int64_t out_cap);
+
+/* Decode one ORC TIMESTAMP column's stream pair through the product's own
+ * decoders: DATA (signed RLEv2 seconds relative to 2015-01-01 UTC) and
+ * SECONDARY (unsigned RLEv2 nanoseconds, trailing zeros removed).
+ *   unit 0: INT64 milliseconds (timestamp(p <= 3)); 1: microseconds.
+ *   mode 0, host (no GPU): the host RLEv2 restatement plus the scalar core
+ *     the kernel shares (orc_timestamp_core.h).
+ *   mode 2, device path: both streams upload as staging does, decode through
+ *     k_rlev2 (the nanos into a scratch) and combine in k_orc_timestamp. The
+ *     device output sits between two 64-element guard zones pre-filled with
+ *     0xA5. Owns its device memory; needs no session.
+ * Writes n_values int64 to `out` (out_cap >= n_values) and returns
+ * n_values. Returns -1 with pmh_last_error() set on a malformed stream, bad
+ * arguments, a HIP error or a refused value ("ORC timestamp refused: ..."
+ * naming a value before 1970 with a fractional second, nanos of 10^9 or
+ * more, or a result outside int64), and -2 when a kernel changed a guard
+ * zone. */
+int64_t pmh_debug_orc_timestamp(const void *data, int64_t data_len,
+                                const void *secondary, int64_t secondary_len,
+                                int64_t n_values, int unit, int mode,
+                                void *out, int64_t out_cap);
 
 /* Parse one deletion vector from a DV index file slice (DeletionFile
  * {path, offset, length}; BitmapDeletionVector.java:98-112 wrapper around

@@ -11,7 +11,10 @@ from .reader import (  # noqa: F401
     interval_partition,
     debug_lookup_probe,
     debug_json_i64,
+    debug_bits,
+    debug_check_column,
     debug_orc_decimal,
+    debug_orc_timestamp,
     debug_orc_ints,
     file_descs_from_metas,
     write_parquet,

@@ -89,8 +89,13 @@ def rewrite(session: Session, file_metas, key_cols, value_cols, out_dir,
                                  valid[s:e] if valid is not None else None))
                 path = os.path.join(out_dir, f"{file_prefix}-{file_idx}.parquet")
                 file_idx += 1
+                # date / time / timestamp annotations come from the batch
+                # (plan.logicals); boolean columns arrive as numpy bool and
+                # are written as BOOLEAN. An ORC-sourced column is written
+                # back as its Parquet mapping, as decimals are
                 write_parquet(path, cols, compression=compression,
-                              dicts=dicts, decimals=decimals)
+                              dicts=dicts, decimals=decimals,
+                              logicals=plan.logicals)
                 sq = seq[s:e]
                 kd = kind[s:e]
                 # minKey/maxKey are the first/last merged rows' full key

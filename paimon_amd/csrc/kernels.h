@@ -6,7 +6,9 @@
 
 #include <cstdint>
 
+#include "bits_core.h"
 #include "orc_decimal_core.h"
+#include "orc_timestamp_core.h"
 
 namespace pmh {
 
@@ -95,7 +97,8 @@ struct Rlev2Chunk {
     uint8_t dense_target;  // 0: contig (positioned); 1: dense buffer
                            // (PRESENT scatter follows); 2: the (run,
                            // column)'s int32 decimal-scale scratch
-                           // (out_start = scratch index)
+                           // (out_start = scratch index); 3: its uint64
+                           // timestamp-nanos scratch (likewise)
     uint8_t _pad[2];
     uint64_t out_addr;     // absolute output base (patched at finalize)
 };
@@ -212,6 +215,19 @@ hipError_t pmh_launch_rlev2(const Rlev2Chunk *chunks, int64_t n_chunks,
 // k_rlev2 launch that fills it, on the same stream.
 hipError_t pmh_launch_orc_varint(const VarintUnit *units, int64_t n_units,
                                  hipStream_t stream);
+
+// Expand BOOLEAN work units (BitsUnit, bits_core.h: Parquet PLAIN bits or
+// ORC boolean byte-RLE runs / literal groups) into 0/1 elements of 1 or 4
+// bytes. One wave per unit; a unit may start at any output index.
+hipError_t pmh_launch_bits_expand(const BitsUnit *units, int64_t n_units,
+                                  hipStream_t stream);
+
+// Combine ORC TIMESTAMP seconds and stored nanos (TsUnit,
+// orc_timestamp_core.h) into INT64 milliseconds / microseconds, in place.
+// Launched after the k_rlev2 launch that decodes both streams, on the same
+// stream. One workgroup per unit.
+hipError_t pmh_launch_orc_timestamp(const TsUnit *units, int64_t n_units,
+                                    hipStream_t stream);
 
 hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
                                 int64_t tile_rows, int64_t n_bounds,

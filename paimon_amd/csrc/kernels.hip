@@ -3206,6 +3206,104 @@ void k_orc_varint(const VarintUnit *units, int64_t n_units) {
     }
 }
 
+// --------------------------------------------------------- k_bits_expand
+//
+// BOOLEAN value decode for both formats (bits_core.h): Parquet PLAIN pages
+// (1 bit per value, LSB first) and ORC boolean byte-RLE units (MSB first,
+// literal bytes or one repeated byte) expand to 0/1 elements, 1 or 4 bytes
+// wide. One 64-lane wave per unit, no LDS, no barrier.
+// A lane owns one OUTPUT group: the 8 elements of an absolutely aligned
+// 8-element block (8 bytes at width 1, 32 bytes at width 4). A unit's first
+// element sits at any index (pages and stripes end anywhere, dense counts
+// under nulls are arbitrary), so with r = that index modulo 8 the group takes
+// the top r bits of source byte g-1 and the low 8 - r bits of byte g. Groups
+// wholly inside the unit store wide (one 8-byte or two 16-byte stores per
+// lane, consecutive lanes consecutive addresses); the first and the last
+// group of a unit may be shared with a neighbouring unit, another wave's, and
+// store element by element inside [out_start, out_start + count) only.
+// Loads are byte loads of the unit's own ceil(count / 8) source bytes:
+// nothing before the unit and nothing of the staging tail pad is touched.
+__launch_bounds__(256) __global__
+void k_bits_expand(const BitsUnit *units, int64_t n_units) {
+    const int wave = (int)(threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63);
+    const int waves = (int)(blockDim.x >> 6);
+    for (int64_t uidx = (int64_t)blockIdx.x * waves + wave; uidx < n_units;
+         uidx += (int64_t)gridDim.x * waves) {
+        const BitsUnit u = units[uidx];
+        const uint8_t *src = (const uint8_t *)u.src;
+        const int r = bits_unit_r(u.out_addr, u.out_start, u.out_esize);
+        const int n_groups = bits_unit_groups(r, u.count);
+        // element index (from out_addr) of group 0's first element: a
+        // multiple of 8 in absolute terms, possibly before out_start
+        const int64_t g0 = u.out_start - r;
+        for (int g = lane; g < n_groups; g += 64) {
+            const uint32_t bits = bits_unit_group(u, src, r, g);
+            const int lo = g == 0 ? r : 0;  // first element of the group
+                                            // that belongs to the unit
+            const int left = r + u.count - 8 * g;
+            const int hi = left < 8 ? left : 8;  // one past the last
+            const uint64_t bytes = bits_spread(bits);
+            if (u.out_esize == 1) {
+                uint8_t *p = (uint8_t *)u.out_addr + (g0 + (int64_t)8 * g);
+                if (lo == 0 && hi == 8) {
+                    *reinterpret_cast<uint64_t *>(p) = bytes;
+                } else {
+                    for (int t = lo; t < hi; t++)
+                        p[t] = (uint8_t)(bytes >> (8 * t));
+                }
+            } else {
+                int32_t *p = (int32_t *)u.out_addr + (g0 + (int64_t)8 * g);
+                if (lo == 0 && hi == 8) {
+                    const uint32_t b0 = (uint32_t)bytes;
+                    const uint32_t b1 = (uint32_t)(bytes >> 32);
+                    uint4 v0, v1;
+                    v0.x = b0 & 1u;
+                    v0.y = (b0 >> 8) & 1u;
+                    v0.z = (b0 >> 16) & 1u;
+                    v0.w = b0 >> 24;
+                    v1.x = b1 & 1u;
+                    v1.y = (b1 >> 8) & 1u;
+                    v1.z = (b1 >> 16) & 1u;
+                    v1.w = b1 >> 24;
+                    reinterpret_cast<uint4 *>(p)[0] = v0;
+                    reinterpret_cast<uint4 *>(p)[1] = v1;
+                } else {
+                    for (int t = lo; t < hi; t++)
+                        p[t] = (int32_t)((bits >> t) & 1u);
+                }
+            }
+        }
+    }
+}
+
+// --------------------------------------------------------- k_orc_timestamp
+//
+// ORC TIMESTAMP combine (orc_timestamp_core.h): k_rlev2 has decoded the DATA
+// stream's int64 seconds to the column (or its dense buffer under PRESENT)
+// and the SECONDARY stream's stored nanos to the (run, column)'s uint64
+// scratch; this elementwise pass replaces each second by the column value
+// in milliseconds or microseconds, in place. One workgroup per unit of
+// <= OTS_UNIT_VALUES values, one value per thread and step, 8-byte loads and
+// stores at consecutive addresses. Refusals OR a bit into the section's
+// error word (only threads that met one issue the atomic).
+__launch_bounds__(256) __global__
+void k_orc_timestamp(const TsUnit *units, int64_t n_units) {
+    for (int64_t uidx = blockIdx.x; uidx < n_units; uidx += gridDim.x) {
+        const TsUnit u = units[uidx];
+        int64_t *out = (int64_t *)u.out_addr + u.out_start;
+        const uint64_t *nanos = (const uint64_t *)u.nanos_addr + u.nanos_start;
+        uint32_t errs = 0;
+        for (int i = (int)threadIdx.x; i < u.count; i += (int)blockDim.x) {
+            int64_t v;
+            const int err = ots_value(out[i], nanos[i], u.unit, &v);
+            if (err) errs |= 1u << (OTS_ERR_SHIFT + err);
+            out[i] = v;
+        }
+        if (errs && u.err_addr) atomicOr((uint32_t *)u.err_addr, errs);
+    }
+}
+
 // ------------------------------------------------------------ DELTA decode
 //
 // Parquet DELTA_BINARY_PACKED (VectorizedDeltaBinaryPackedReader.java /
@@ -4480,6 +4578,24 @@ hipError_t pmh_launch_orc_varint(const VarintUnit *units, int64_t n_units,
     int64_t want = (n_units + waves_per_block - 1) / waves_per_block;
     int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
     hipLaunchKernelGGL(k_orc_varint, dim3(blocks), dim3(256), 0, stream,
+                       units, n_units);
+    return hipGetLastError();
+}
+
+hipError_t pmh_launch_bits_expand(const BitsUnit *units, int64_t n_units,
+                                  hipStream_t stream) {
+    int waves_per_block = 4;  // 256 threads
+    int64_t want = (n_units + waves_per_block - 1) / waves_per_block;
+    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    hipLaunchKernelGGL(k_bits_expand, dim3(blocks), dim3(256), 0, stream,
+                       units, n_units);
+    return hipGetLastError();
+}
+
+hipError_t pmh_launch_orc_timestamp(const TsUnit *units, int64_t n_units,
+                                    hipStream_t stream) {
+    int blocks = n_units < 4096 ? (int)(n_units ? n_units : 1) : 4096;
+    hipLaunchKernelGGL(k_orc_timestamp, dim3(blocks), dim3(256), 0, stream,
                        units, n_units);
     return hipGetLastError();
 }

@@ -97,6 +97,10 @@ bool is_orc_file(const uint8_t *data, int64_t size) {
     return size > 16 && memcmp(data, "ORC", 3) == 0;
 }
 
+bool orc_timezone_is_utc(const std::string &tz) {
+    return tz.empty() || tz == "UTC" || tz == "GMT";
+}
+
 const OrcStream *orc_find_stream(const OrcStripe &st, int column, int kind) {
     for (const auto &s : st.streams)
         if (s.column == column && s.kind == kind) return &s;
@@ -206,6 +210,9 @@ OrcFileMeta parse_orc_meta(const uint8_t *data, int64_t size) {
                             pb_parse((const uint8_t *)eb.bin.data(),
                                      eb.bin.size()),
                             1));
+                auto tzit = spf.find(3);  // writerTimezone
+                if (tzit != spf.end() && !tzit->second.empty())
+                    st.writer_timezone = tzit->second.back().bin;
                 out.stripes.push_back(std::move(st));
             }
         }

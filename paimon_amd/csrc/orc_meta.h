@@ -23,8 +23,11 @@ enum OrcTypeKind {
     ORC_FLOAT = 5,
     ORC_DOUBLE = 6,
     ORC_STRING = 7,
+    ORC_TIMESTAMP = 9,  // relative to 2015-01-01 in the WRITER's timezone
     ORC_STRUCT = 12,
     ORC_DECIMAL = 14,
+    ORC_DATE = 15,      // signed RLEv2 days since 1970-01-01
+    ORC_TIMESTAMP_INSTANT = 18,  // timestamp with local time zone: UTC
 };
 
 enum OrcStreamKind {
@@ -32,8 +35,13 @@ enum OrcStreamKind {
     ORC_STREAM_DATA = 1,
     ORC_STREAM_LENGTH = 2,
     ORC_STREAM_DICTIONARY = 3,
-    ORC_STREAM_SECONDARY = 5,  // decimal: per-value scale, signed RLEv2
+    ORC_STREAM_SECONDARY = 5,  // decimal: per-value scale, signed RLEv2;
+                               // timestamp: nanoseconds, unsigned RLEv2
 };
+
+// StripeFooter.writerTimezone names UTC (TIMESTAMP columns of any other
+// zone are refused at staging): empty, "UTC" or "GMT".
+bool orc_timezone_is_utc(const std::string &tz);
 
 struct OrcStream {
     int kind = 0;
@@ -50,6 +58,7 @@ struct OrcStripe {
     int64_t num_rows = 0;
     std::vector<OrcStream> streams;
     std::vector<int> encodings;  // per column id
+    std::string writer_timezone;  // StripeFooter.writerTimezone ("" = none)
 };
 
 struct OrcFileMeta {

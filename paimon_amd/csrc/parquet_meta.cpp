@@ -176,6 +176,25 @@ ParquetFileMeta parse_parquet_footer(const uint8_t *data, int64_t size) {
             int rep = se.count(3) ? (int)se.at(3).i : 0;
             out.max_def_levels.push_back(rep == 1 ? 1 : 0);
             out.phys_types.push_back(se.count(1) ? (int)se.at(1).i : -1);
+            // 6 = converted_type; 10 = logicalType, a union: the one field
+            // set names the type, TIME (7) and TIMESTAMP (8) carry
+            // {1: isAdjustedToUTC, 2: unit (union 1 MILLIS 2 MICROS 3 NANOS)}
+            out.converted_types.push_back(se.count(6) ? (int)se.at(6).i : -1);
+            int lkind = 0, lunit = PQ_UNIT_NONE, lutc = 0;
+            if (se.count(10) && se.at(10).st && !se.at(10).st->empty()) {
+                const auto &un = *se.at(10).st;
+                lkind = un.begin()->first;
+                const TValue &lt = un.begin()->second;
+                if ((lkind == LOGICAL_TIME || lkind == LOGICAL_TIMESTAMP) &&
+                    lt.st) {
+                    lutc = (int)lt.fi(1, 0);
+                    const TValue &tu = lt.f(2);
+                    if (tu.st && !tu.st->empty()) lunit = tu.st->begin()->first;
+                }
+            }
+            out.logical_kinds.push_back(lkind);
+            out.logical_units.push_back(lunit);
+            out.logical_utc.push_back(lutc);
             if (se.count(5) && se.at(5).i > 0) {
                 out.error = "nested parquet schemas unsupported (flat KeyValue rows only)";
                 return out;

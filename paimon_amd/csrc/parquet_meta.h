@@ -42,6 +42,23 @@ enum ParquetPhysType {
     PHYS_FIXED_LEN_BYTE_ARRAY = 7,
 };
 
+// parquet.thrift ConvertedType values and LogicalType union members of the
+// date / time types, and the TimeUnit union members
+enum ParquetAnnotation {
+    CONV_DATE = 6,
+    CONV_TIME_MILLIS = 7,
+    CONV_TIME_MICROS = 8,
+    CONV_TIMESTAMP_MILLIS = 9,
+    CONV_TIMESTAMP_MICROS = 10,
+    LOGICAL_DATE = 6,
+    LOGICAL_TIME = 7,
+    LOGICAL_TIMESTAMP = 8,
+    PQ_UNIT_NONE = 0,
+    PQ_UNIT_MILLIS = 1,
+    PQ_UNIT_MICROS = 2,
+    PQ_UNIT_NANOS = 3,
+};
+
 struct PageMeta {
     int page_type;        // 0 data v1, 2 dictionary, 3 data v2
     int64_t header_off;   // absolute file offset of page header
@@ -76,6 +93,12 @@ struct ParquetFileMeta {
     std::vector<std::string> schema_names;  // leaf columns, flat schema
     std::vector<int> max_def_levels;        // 1 for OPTIONAL, 0 for REQUIRED
     std::vector<int> phys_types;
+    // per leaf, the schema element's annotation: converted_type (-1 = none)
+    // and logicalType reduced to (union member, time unit, isAdjustedToUTC)
+    std::vector<int> converted_types;
+    std::vector<int> logical_kinds;  // LogicalType field id; 0 = none
+    std::vector<int> logical_units;  // PQ_UNIT_* for TIME / TIMESTAMP
+    std::vector<int> logical_utc;    // isAdjustedToUTC
     std::vector<RowGroupMeta> row_groups;
     std::string error;  // non-empty on failure
 

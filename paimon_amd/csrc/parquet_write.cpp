@@ -6,7 +6,9 @@
 // ParquetWriterFactory.java + the vendored parquet-mr writer) as used by
 // KeyValueDataFileWriter (io/KeyValueDataFileWriter.java:121-170) under
 // CompactRewriter. v1 matrix: INT8/16 (stored INT32), INT32, INT64, FLOAT,
-// DOUBLE; REQUIRED or OPTIONAL (byte validity -> RLE/bit-packed def levels);
+// DOUBLE, BOOLEAN (PLAIN, bit-packed), the DATE / TIME(MILLIS) /
+// TIMESTAMP(MILLIS|MICROS) annotations on INT32/INT64;
+// REQUIRED or OPTIONAL (byte validity -> RLE/bit-packed def levels);
 // one PLAIN data page per `page_rows`; UNCOMPRESSED or ZSTD pages (host
 // compress; no dictionary — GPU-side encode is roadmap §8f.1). Readable by
 // parquet-mr/pyarrow and by this library's own reader (tests pin both).
@@ -81,19 +83,89 @@ int phys_of(int dtype) {
     case 5: return PHYS_FLOAT;
     case 6: return PHYS_DOUBLE;
     case 7: return PHYS_BYTE_ARRAY;  // dictionary string
+    case 8: return PHYS_BOOLEAN;
     }
     return -1;
 }
 
+// pmh_logical values (paimon_hip.h) as the writer sees them
+enum {
+    LT_DATE = 1,
+    LT_TIME_MILLIS = 2,
+    LT_TS_MILLIS = 3,
+    LT_TS_MICROS = 4,
+    LT_TS_LTZ_MILLIS = 5,
+    LT_TS_LTZ_MICROS = 6,
+};
+
 int converted_of(const PwCol &c) {  // ConvertedType; -1 = none
     if (c.precision > 0) return 5;  // DECIMAL (INT32/INT64 physical, as
                                     // ParquetSchemaConverter.java:153-171)
+    switch (c.logical) {            // ParquetSchemaConverter.java:126-216
+    case LT_DATE: return CONV_DATE;
+    case LT_TIME_MILLIS: return CONV_TIME_MILLIS;
+    case LT_TS_MILLIS:
+    case LT_TS_LTZ_MILLIS: return CONV_TIMESTAMP_MILLIS;
+    case LT_TS_MICROS:
+    case LT_TS_LTZ_MICROS: return CONV_TIMESTAMP_MICROS;
+    }
     switch (c.dtype) {
     case 1: return 15;  // INT_8
     case 2: return 16;  // INT_16
     case 7: return 0;   // UTF8
     }
     return -1;
+}
+
+// SchemaElement.logicalType (field 10, a union) for the date / time types:
+// DATE = member 6, an empty struct; TIME = 7 and TIMESTAMP = 8 carry
+// {1: isAdjustedToUTC, 2: unit}, unit a union of empty structs (1 MILLIS,
+// 2 MICROS). TIME is written adjusted to UTC and timestamps by their ltz
+// flag, as ParquetSchemaConverter.java:195-216, 306-323 does.
+void logical_type(TC &t, int &last, int logical) {
+    t.field(last, 10, 12);
+    int lu = 0;
+    if (logical == LT_DATE) {
+        t.field(lu, LOGICAL_DATE, 12);
+        t.stop();
+    } else {
+        const bool is_time = logical == LT_TIME_MILLIS;
+        const bool utc = is_time || logical == LT_TS_LTZ_MILLIS ||
+                         logical == LT_TS_LTZ_MICROS;
+        const bool micros =
+            logical == LT_TS_MICROS || logical == LT_TS_LTZ_MICROS;
+        t.field(lu, is_time ? LOGICAL_TIME : LOGICAL_TIMESTAMP, 12);
+        int lt = 0;
+        t.field(lt, 1, utc ? 1 : 2);  // bool: the type nibble is the value
+        t.field(lt, 2, 12);           // unit
+        {
+            int ln = 0;
+            t.field(ln, micros ? PQ_UNIT_MICROS : PQ_UNIT_MILLIS, 12);
+            t.stop();  // the empty MilliSeconds / MicroSeconds struct
+            t.stop();  // TimeUnit
+        }
+        t.stop();  // TimeType / TimestampType
+    }
+    t.stop();  // LogicalType
+}
+
+// PLAIN boolean payload for rows [s, e): non-null values only, 1 bit per
+// value, LSB first, zero-padded to a whole byte (every page restarts on a
+// byte boundary).
+void encode_bools(const PwCol &c, int64_t s, int64_t e, std::string &out) {
+    const uint8_t *d = (const uint8_t *)c.data;
+    uint8_t acc = 0;
+    int nbits = 0;
+    for (int64_t i = s; i < e; i++) {
+        if (c.valid && !c.valid[i]) continue;
+        if (d[i]) acc |= (uint8_t)(1u << nbits);
+        if (++nbits == 8) {
+            out.push_back((char)acc);
+            acc = 0;
+            nbits = 0;
+        }
+    }
+    if (nbits) out.push_back((char)acc);
 }
 
 // RLE/bit-packed hybrid id stream for RLE_DICTIONARY pages: a leading
@@ -244,8 +316,23 @@ bool write_parquet(const std::vector<PwCol> &cols, int64_t n_rows,
         if (phys_of(c.dtype) < 0) {
             err = "unsupported dtype " + std::to_string(c.dtype) +
                   " for parquet write (v1 matrix: int8..int64/float/double/"
-                  "decimal<=18/dictionary string)";
+                  "decimal<=18/dictionary string/boolean)";
             return false;
+        }
+        if (c.logical) {
+            const int want = c.logical == LT_DATE ||
+                                     c.logical == LT_TIME_MILLIS
+                                 ? 3
+                                 : 4;
+            if (c.logical < 0 || c.logical > LT_TS_LTZ_MICROS ||
+                c.dtype != want || c.precision > 0) {
+                err = "column '" + c.name + "': logical annotation " +
+                      std::to_string(c.logical) + " does not fit dtype " +
+                      std::to_string(c.dtype) +
+                      " (date/time ride int32, timestamps int64, neither "
+                      "is a decimal)";
+                return false;
+            }
         }
         if (c.dtype == 7 &&
             (!c.dict_data || !c.dict_offsets || c.dict_len <= 0)) {
@@ -312,6 +399,7 @@ bool write_parquet(const std::vector<PwCol> &cols, int64_t n_rows,
                 std::string payload;
                 if (c.valid) encode_def_levels(c.valid + p0, p1 - p0, payload);
                 if (dict) encode_dict_ids(c, p0, p1, payload);
+                else if (c.dtype == 8) encode_bools(c, p0, p1, payload);
                 else encode_values(c, p0, p1, payload);
                 payloads.push_back(std::move(payload));
                 prows.push_back(p1 - p0);
@@ -393,6 +481,7 @@ bool write_parquet(const std::vector<PwCol> &cols, int64_t n_rows,
                 g.i32(lf, 7, c.scale);
                 g.i32(lf, 8, c.precision);
             }
+            if (c.logical) logical_type(g, lf, c.logical);
             g.stop();
         }
     }

@@ -21,6 +21,10 @@ struct PwCol {
     // DECIMAL(p,s) annotation on INT32/INT64 (0 = plain integer)
     int32_t precision = 0;
     int32_t scale = 0;
+    // date / time / timestamp annotation on INT32/INT64: the values of
+    // enum pmh_logical (paimon_hip.h); 0 = none. dtype 8 (boolean): data is
+    // one 0/1 byte per row, written bit-packed
+    int32_t logical = 0;
 };
 
 // codec: CODEC_UNCOMPRESSED or CODEC_ZSTD (parquet_meta.h values)

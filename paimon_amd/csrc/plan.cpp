@@ -478,6 +478,13 @@ struct ColSpec {
     int stored_esize;  // parquet physical width (TINYINT stored as INT32)
     int precision = 0;  // DECIMAL(p,s) annotation on INT32/INT64
     int scale = 0;
+    // date / time / timestamp annotation on INT32/INT64 (enum pmh_logical)
+    int logical = 0;
+    // BOOLEAN: dtype is PMH_DT_INT8 inside the pipeline, so the column
+    // stages at the 4-byte stored width every merge and emit kernel loads
+    // and narrows to one 0/1 byte on emit, as TINYINT does; the batch
+    // reports PMH_DT_BOOL
+    bool is_bool = false;
 };
 
 // Plan-level GLOBAL dictionary for one string column: per-file parquet
@@ -569,6 +576,17 @@ struct RunCol {
     std::vector<VarintUnit> varint_host;
     int64_t scale_rows = 0;
     int32_t *scale_dev = nullptr;
+    // BOOLEAN (parquet PLAIN bits / ORC boolean byte-RLE): k_bits_expand
+    // work units; the encoded bytes stay in HBM and expand at read time
+    std::vector<BitsUnit> bits_host;
+    // ORC TIMESTAMP: the SECONDARY stream's stored nanos decode through
+    // k_rlev2 into nanos_dev, the (run, column)'s uint64 scratch
+    // (nanos_rows values); k_orc_timestamp then combines them with the
+    // seconds k_rlev2 wrote to the column. Units carry scratch INDICES in
+    // nanos_start and get their addresses at finalize
+    std::vector<TsUnit> ts_host;
+    int64_t nanos_rows = 0;
+    uint64_t *nanos_dev = nullptr;
     // parquet DELTA_BINARY_PACKED pages (decoded on GPU at read time)
     std::vector<DeltaChunk> delta_host;
     std::vector<DeltaStream> dstreams_host;
@@ -646,6 +664,10 @@ struct Section {
     int64_t n_rlev2 = 0;
     VarintUnit *varint_all = nullptr;
     int64_t n_varint = 0;
+    BitsUnit *bits_all = nullptr;
+    int64_t n_bits = 0;
+    TsUnit *ts_all = nullptr;
+    int64_t n_ts = 0;
     DeltaChunk *delta_all = nullptr;
     int64_t n_delta = 0;
     DeltaStream *dstreams_all = nullptr;
@@ -769,6 +791,82 @@ static bool parse_decimal(const std::string &s, int *p, int *sc) {
     return sscanf(s.c_str(), "decimal(%d,%d)", p, sc) == 2;
 }
 
+// "boolean", "date", "time", "timestamp[(p)]", "timestamp_ltz[(p)]": the
+// reference's physical mapping (ParquetSchemaConverter.java:126-216,
+// 306-323; OrcTypeUtil.java:67-114) — boolean is its own column, the others
+// ride INT32/INT64 with a pmh_logical annotation; a bare timestamp is
+// timestamp(6). Returns 0 = none of these, 1 = parsed into cs, -1 = refused
+// (error set): precision above 6 would be parquet INT96 / sub-microsecond ORC.
+static int parse_bool_or_temporal(const std::string &s, ColSpec &cs) {
+    if (s == "boolean" || s == "bool") {
+        cs.dtype = PMH_DT_INT8;
+        cs.is_bool = true;
+        return 1;
+    }
+    if (s == "date") {
+        cs.dtype = PMH_DT_INT32;
+        cs.logical = PMH_LT_DATE;
+        return 1;
+    }
+    if (s == "time") {
+        cs.dtype = PMH_DT_INT32;
+        cs.logical = PMH_LT_TIME_MILLIS;
+        return 1;
+    }
+    bool ltz = false;
+    std::string rest;
+    if (s.rfind("timestamp_ltz", 0) == 0) {
+        ltz = true;
+        rest = s.substr(13);
+    } else if (s.rfind("timestamp", 0) == 0) {
+        rest = s.substr(9);
+    } else {
+        return 0;
+    }
+    int p = 6;
+    if (!rest.empty()) {
+        int used = 0;
+        if (sscanf(rest.c_str(), "(%d)%n", &p, &used) != 1 ||
+            used != (int)rest.size())
+            return 0;
+    }
+    if (p < 0 || p > 6) {
+        set_error("%s: timestamp precision %d is not supported (0..6: INT64 "
+                  "milliseconds / microseconds; parquet INT96 and "
+                  "sub-microsecond ORC timestamps are out of scope)",
+                  s.c_str(), p);
+        return -1;
+    }
+    cs.dtype = PMH_DT_INT64;
+    cs.logical = p <= 3 ? (ltz ? PMH_LT_TIMESTAMP_LTZ_MILLIS
+                               : PMH_LT_TIMESTAMP_MILLIS)
+                        : (ltz ? PMH_LT_TIMESTAMP_LTZ_MICROS
+                               : PMH_LT_TIMESTAMP_MICROS);
+    return 1;
+}
+
+static bool logical_is_timestamp(int lt) {
+    return lt >= PMH_LT_TIMESTAMP_MILLIS && lt <= PMH_LT_TIMESTAMP_LTZ_MICROS;
+}
+static bool logical_is_ltz(int lt) {
+    return lt == PMH_LT_TIMESTAMP_LTZ_MILLIS ||
+           lt == PMH_LT_TIMESTAMP_LTZ_MICROS;
+}
+static bool logical_is_micros(int lt) {
+    return lt == PMH_LT_TIMESTAMP_MICROS || lt == PMH_LT_TIMESTAMP_LTZ_MICROS;
+}
+static const char *logical_name(int lt) {
+    switch (lt) {
+    case PMH_LT_DATE: return "date";
+    case PMH_LT_TIME_MILLIS: return "time";
+    case PMH_LT_TIMESTAMP_MILLIS: return "timestamp(3)";
+    case PMH_LT_TIMESTAMP_MICROS: return "timestamp(6)";
+    case PMH_LT_TIMESTAMP_LTZ_MILLIS: return "timestamp_ltz(3)";
+    case PMH_LT_TIMESTAMP_LTZ_MICROS: return "timestamp_ltz(6)";
+    }
+    return "none";
+}
+
 static int dtype_out_esize(int dt) {
     switch (dt) {
     case PMH_DT_INT8: return 1;
@@ -809,6 +907,94 @@ static int expected_phys(int dtype) {
     case PMH_DT_STRING: return PHYS_BYTE_ARRAY;
     }
     return -1;
+}
+
+static const char *pq_unit_name(int u) {
+    return u == PQ_UNIT_MILLIS   ? "MILLIS"
+           : u == PQ_UNIT_MICROS ? "MICROS"
+           : u == PQ_UNIT_NANOS  ? "NANOS"
+                                 : "none";
+}
+
+// A column declared boolean / date / time / timestamp against the parquet
+// file's schema element: the physical type has to be the reference's mapping
+// and, for the annotated types, the annotation has to say the same thing.
+// The timestamp unit is the one mismatch that would otherwise mis-scale
+// every value silently. Each refusal has its own text.
+static bool check_parquet_declared(const std::string &path, const ColSpec &cs,
+                                   const ParquetFileMeta &m, int leaf) {
+    if (!cs.is_bool && !cs.logical) return true;
+    const int phys = (int)m.phys_types.size() > leaf ? m.phys_types[leaf] : -1;
+    const int want = cs.is_bool ? PHYS_BOOLEAN : expected_phys(cs.dtype);
+    const char *decl = cs.is_bool ? "boolean" : logical_name(cs.logical);
+    if (phys != want) {
+        set_error("%s: column %s declared %s but the file's physical type "
+                  "is %d (expect %d)", path.c_str(), cs.name.c_str(), decl,
+                  phys, want);
+        return false;
+    }
+    if (cs.is_bool) return true;
+    const int conv = m.converted_types[leaf];
+    const int lk = m.logical_kinds[leaf];
+    if (cs.logical == PMH_LT_DATE) {
+        if (lk != LOGICAL_DATE && conv != CONV_DATE) {
+            set_error("%s: column %s declared date but the file column "
+                      "carries no DATE annotation", path.c_str(),
+                      cs.name.c_str());
+            return false;
+        }
+        return true;
+    }
+    int unit = PQ_UNIT_NONE;
+    if (cs.logical == PMH_LT_TIME_MILLIS) {
+        if (lk == LOGICAL_TIME) unit = m.logical_units[leaf];
+        else if (conv == CONV_TIME_MILLIS) unit = PQ_UNIT_MILLIS;
+        else if (conv == CONV_TIME_MICROS) unit = PQ_UNIT_MICROS;
+        if (unit == PQ_UNIT_NONE) {
+            set_error("%s: column %s declared time but the file column "
+                      "carries no TIME annotation", path.c_str(),
+                      cs.name.c_str());
+            return false;
+        }
+        if (unit != PQ_UNIT_MILLIS) {
+            set_error("%s: column %s declared time (INT32 milliseconds) but "
+                      "the file's TIME unit is %s", path.c_str(),
+                      cs.name.c_str(), pq_unit_name(unit));
+            return false;
+        }
+        return true;
+    }
+    if (lk == LOGICAL_TIMESTAMP) unit = m.logical_units[leaf];
+    else if (conv == CONV_TIMESTAMP_MILLIS) unit = PQ_UNIT_MILLIS;
+    else if (conv == CONV_TIMESTAMP_MICROS) unit = PQ_UNIT_MICROS;
+    if (unit == PQ_UNIT_NONE) {
+        set_error("%s: column %s declared %s but the file column carries no "
+                  "TIMESTAMP annotation", path.c_str(), cs.name.c_str(),
+                  decl);
+        return false;
+    }
+    const int want_unit =
+        logical_is_micros(cs.logical) ? PQ_UNIT_MICROS : PQ_UNIT_MILLIS;
+    if (unit != want_unit) {
+        set_error("%s: column %s declared %s (%s) but the file's TIMESTAMP "
+                  "unit is %s", path.c_str(), cs.name.c_str(), decl,
+                  pq_unit_name(want_unit), pq_unit_name(unit));
+        return false;
+    }
+    return true;
+}
+
+// A boolean column's page: PLAIN (bit-packed) v1 data pages only.
+static bool check_bool_page(const std::string &path, const ColSpec &cs,
+                            const PageMeta &pg) {
+    if (pg.page_type == 0 && pg.encoding == ENC_PLAIN) return true;
+    const std::string enc = pg.page_type == 2      ? "dictionary"
+                            : pg.encoding == ENC_RLE ? "RLE"
+                                : std::to_string(pg.encoding);
+    set_error("%s col %s: boolean pages in %s encoding are not supported "
+              "(PLAIN bit-packed pages only; RLE is what data page v2 "
+              "writers emit)", path.c_str(), cs.name.c_str(), enc.c_str());
+    return false;
 }
 
 // Walk a def-level stream (bit width 1): emit device work chunks with
@@ -1197,8 +1383,14 @@ static int rlev2_closest_fixed_bits(int n) {
     return 64;
 }
 
-static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
-                         std::vector<uint64_t> &out) {
+// is_signed: SHORT_REPEAT / DIRECT values and the DELTA base are zigzag
+// (signed streams: the ORC TIMESTAMP seconds of the debug entry's host mode);
+// the values then come back as the int64 bit patterns.
+static bool host_rlev2(const uint8_t *s, int64_t len, int64_t n,
+                       bool is_signed, std::vector<uint64_t> &out) {
+    auto unzz = [&](uint64_t v) -> uint64_t {
+        return is_signed ? (v >> 1) ^ (0 - (v & 1)) : v;
+    };
     out.clear();
     if (n > 0) out.reserve(n);
     int64_t p = 0;
@@ -1222,6 +1414,7 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
             if (p + 1 + w > len) return false;
             uint64_t v = 0;
             for (int i = 0; i < w; i++) v = (v << 8) | s[p + 1 + i];
+            v = unzz(v);
             for (int i = 0; i < cnt; i++) out.push_back(v);
             p += 1 + w;
         } else if (mode == 1) {  // DIRECT
@@ -1231,7 +1424,7 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
             int64_t nbytes = ((int64_t)cnt * w + 7) / 8;
             if (p + 2 + nbytes > len) return false;
             for (int i = 0; i < cnt; i++)
-                out.push_back(bits_be(p + 2, (int64_t)i * w, w));
+                out.push_back(unzz(bits_be(p + 2, (int64_t)i * w, w)));
             p += 2 + nbytes;
         } else if (mode == 2) {  // PATCHED_BASE
             if (p + 4 > len) return false;
@@ -1293,6 +1486,7 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
                 sh += 7;
             }
             int64_t d0 = (int64_t)(zd >> 1) ^ -(int64_t)(zd & 1);
+            base = unzz(base);
             out.push_back(base);
             int64_t cur = (int64_t)base;
             if (cnt > 1) {
@@ -1320,6 +1514,16 @@ static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
         }
     }
     return n < 0 || (int64_t)out.size() >= n;
+}
+
+static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
+                         std::vector<uint64_t> &out) {
+    return host_rlev2(s, len, n, false, out);
+}
+
+static bool host_rlev2_s(const uint8_t *s, int64_t len, int64_t n,
+                         std::vector<uint64_t> &out) {
+    return host_rlev2(s, len, n, true, out);
 }
 
 static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
@@ -1581,6 +1785,66 @@ static std::string orc_decimal_error(uint32_t err_word) {
     return m;
 }
 
+// The decimal bits of an error word: ODC_ERR_SHIFT + 1 .. + 7 (the
+// timestamp bits sit above them, from OTS_ERR_SHIFT on).
+static uint32_t orc_decimal_bits(uint32_t err_word) {
+    return (err_word >> ODC_ERR_SHIFT) & 0xFFu;
+}
+
+// Message for the ORC timestamp bits of a section's device error word
+// (k_orc_timestamp ORs 1 << (OTS_ERR_SHIFT + OTS_ERR_*)).
+static std::string orc_timestamp_error(uint32_t err_word) {
+    std::string m = "ORC timestamp refused:";
+    const char *sep = " ";
+    for (int code = 1; code <= OTS_ERR_LAST; code++)
+        if (err_word & (1u << (OTS_ERR_SHIFT + code))) {
+            m += sep;
+            m += ots_err_text(code);
+            sep = "; ";
+        }
+    return m;
+}
+
+// boolean / date / time / timestamp against one stripe of an ORC file: the
+// declared type and the ORC kind have to be the reference's mapping
+// (OrcTypeUtil.java:67-114), both ways round, and a TIMESTAMP stripe has to
+// be written in UTC.
+static bool check_orc_declared(const std::string &path, const ColSpec &cs,
+                               int ckind, const OrcStripe &st) {
+    const bool k_ts = ckind == ORC_TIMESTAMP || ckind == ORC_TIMESTAMP_INSTANT;
+    int want = -1;
+    if (cs.is_bool) want = ORC_BOOLEAN;
+    else if (cs.logical == PMH_LT_DATE) want = ORC_DATE;
+    else if (cs.logical == PMH_LT_TIME_MILLIS) want = ORC_INT;
+    else if (logical_is_timestamp(cs.logical))
+        want = logical_is_ltz(cs.logical) ? ORC_TIMESTAMP_INSTANT
+                                          : ORC_TIMESTAMP;
+    if (want >= 0 && ckind != want) {
+        set_error("%s col %s: declared %s but ORC kind is %d (expect %d)",
+                  path.c_str(), cs.name.c_str(),
+                  cs.is_bool ? "boolean" : logical_name(cs.logical), ckind,
+                  want);
+        return false;
+    }
+    if (want < 0 && (ckind == ORC_BOOLEAN || ckind == ORC_DATE || k_ts)) {
+        set_error("%s col %s: ORC %s column read as another type",
+                  path.c_str(), cs.name.c_str(),
+                  ckind == ORC_BOOLEAN ? "BOOLEAN"
+                  : ckind == ORC_DATE  ? "DATE"
+                                       : "TIMESTAMP");
+        return false;
+    }
+    if (ckind == ORC_TIMESTAMP && !orc_timezone_is_utc(st.writer_timezone)) {
+        // TIMESTAMP values are relative to 2015-01-01 in the WRITER's zone;
+        // TIMESTAMP_INSTANT is always UTC
+        set_error("%s col %s: ORC TIMESTAMP written in timezone '%s' is not "
+                  "supported (UTC / GMT only)", path.c_str(),
+                  cs.name.c_str(), st.writer_timezone.c_str());
+        return false;
+    }
+    return true;
+}
+
 // Stage one ORC file's stripes for the required columns.
 static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                            const StagedFile &sf, Run &run, int64_t row_base) {
@@ -1641,6 +1905,7 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                     return false;
                 }
             }
+            if (!check_orc_declared(fd.path, cols[c], ckind, st)) return false;
             const int stored = cols[c].stored_esize;
             const OrcStream *data = orc_find_stream(st, cid, ORC_STREAM_DATA);
             const OrcStream *present =
@@ -1668,6 +1933,21 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                               "supported (DIRECT_V2 only; RLEv1 scales are "
                               "out of scope)", fd.path.c_str(),
                               cols[c].name.c_str(), cenc);
+                    return false;
+                }
+                secondary = orc_find_stream(st, cid, ORC_STREAM_SECONDARY);
+                if (!secondary) {
+                    set_error("%s col %s: SECONDARY stream missing",
+                              fd.path.c_str(), cols[c].name.c_str());
+                    return false;
+                }
+            }
+            if (ckind == ORC_TIMESTAMP || ckind == ORC_TIMESTAMP_INSTANT) {
+                if (cenc != 2) {
+                    set_error("%s col %s: ORC TIMESTAMP column encoding %d "
+                              "not supported (DIRECT_V2 only; RLEv1 "
+                              "timestamps are out of scope)",
+                              fd.path.c_str(), cols[c].name.c_str(), cenc);
                     return false;
                 }
                 secondary = orc_find_stream(st, cid, ORC_STREAM_SECONDARY);
@@ -2011,12 +2291,109 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                         vu.scale_addr =
                             (uint64_t)(1 + sc0 + (vu.out_start - dense0));
                     }
+            } else if (ckind == ORC_TIMESTAMP ||
+                       ckind == ORC_TIMESTAMP_INSTANT) {
+                const uint8_t *sec_ptr = sf.data.data() + secondary->offset;
+                int64_t sec_len = secondary->length;
+                std::vector<uint8_t> sec_dec;
+                if (om.compression != 0) {
+                    std::string cerr;
+                    if (!orc_decompress(sec_ptr, sec_len, om.compression,
+                                        om.compression_block_size, sec_dec,
+                                        cerr)) {
+                        set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
+                                  cols[c].name.c_str(), cerr.c_str());
+                        return false;
+                    }
+                    sec_ptr = sec_dec.data();
+                    sec_len = (int64_t)sec_dec.size();
+                }
+                // SECONDARY: unsigned RLEv2 stored nanos, through k_rlev2
+                // into the (run, column) nanos scratch
+                std::vector<Rlev2Chunk> sch;
+                const int64_t n0 = rc.nanos_rows;
+                if (!prescan_rlev2(sec_ptr, sec_len, n_dense, 0, 8, 3, 0, n0,
+                                   sch)) {
+                    set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
+                              cols[c].name.c_str(),
+                              std::string(last_error()).c_str());
+                    return false;
+                }
+                int64_t n_end = n0;
+                for (const auto &k : sch) n_end = k.out_start + k.count;
+                // the scratch is sized by the value count: a stream whose
+                // last run decodes past it is refused
+                if (n_end != n0 + n_dense) {
+                    set_error("%s col %s: SECONDARY stream holds %lld nanos "
+                              "for %lld values", fd.path.c_str(),
+                              cols[c].name.c_str(), (long long)(n_end - n0),
+                              (long long)n_dense);
+                    return false;
+                }
+                void *sdev = plan->bufs.alloc(sec_len + 16);
+                if (!sdev) return false;
+                if (sec_len && hipMemcpy(sdev, sec_ptr, sec_len,
+                                         hipMemcpyHostToDevice) !=
+                                   hipSuccess) {
+                    set_error("H2D failed");
+                    return false;
+                }
+                plan->encoded_bytes_total += sec_len;
+                for (auto &k : sch) {
+                    k.src += (uint64_t)sdev;
+                    if (k.kind == 2) k.patch_src += (uint64_t)sdev;
+                }
+                // DATA: signed RLEv2 seconds relative to 2015-01-01, to the
+                // column (or its dense buffer) as int64
+                const size_t v0 = rc.rlev2_host.size();
+                ok = prescan_rlev2(data_ptr, data_len, n_dense, 1, 8,
+                                   dense_target, (uint64_t)dev, dense0,
+                                   rc.rlev2_host);
+                if (ok) {
+                    int64_t d_end = dense0;
+                    for (size_t i = v0; i < rc.rlev2_host.size(); i++)
+                        d_end = rc.rlev2_host[i].out_start +
+                                rc.rlev2_host[i].count;
+                    if (d_end != dense0 + n_dense) {
+                        set_error("%s col %s: DATA stream holds %lld seconds "
+                                  "for %lld values", fd.path.c_str(),
+                                  cols[c].name.c_str(),
+                                  (long long)(d_end - dense0),
+                                  (long long)n_dense);
+                        return false;
+                    }
+                    rc.rlev2_host.insert(rc.rlev2_host.end(), sch.begin(),
+                                         sch.end());
+                    rc.nanos_rows += n_dense;
+                    for (int64_t d = 0; d < n_dense; d += OTS_UNIT_VALUES) {
+                        TsUnit tu{};
+                        tu.out_start = dense0 + d;
+                        tu.nanos_start = n0 + d;
+                        tu.count = (int32_t)std::min<int64_t>(
+                            OTS_UNIT_VALUES, n_dense - d);
+                        tu.unit = logical_is_micros(cols[c].logical)
+                                      ? OTS_UNIT_MICROS
+                                      : OTS_UNIT_MILLIS;
+                        tu.dense_target = (uint8_t)dense_target;
+                        rc.ts_host.push_back(tu);
+                    }
+                }
+            } else if (ckind == ORC_BOOLEAN) {
+                // DATA: byte-RLE over MSB-first bytes; one unit per run or
+                // literal group, expanded by k_bits_expand at read time
+                const char *why = "";
+                ok = prescan_boolrle(data_ptr, data_len, n_dense, stored,
+                                     dense_target, (uint64_t)dev, dense0,
+                                     rc.bits_host, &why);
+                if (!ok)
+                    set_error("%s col %s: %s", fd.path.c_str(),
+                              cols[c].name.c_str(), why);
             } else if (ckind == ORC_BYTE) {
                 ok = prescan_byterle(data_ptr, data_len, n_dense, stored,
                                      dense_target, (uint64_t)dev, dense0,
                                      rc.rlev2_host);
             } else if (ckind == ORC_SHORT || ckind == ORC_INT ||
-                       ckind == ORC_LONG) {
+                       ckind == ORC_LONG || ckind == ORC_DATE) {
                 ok = prescan_rlev2(data_ptr, data_len, n_dense, 1, stored,
                                    dense_target, (uint64_t)dev, dense0,
                                    rc.rlev2_host);
@@ -2154,6 +2531,12 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                           cols[c].name.c_str());
                 return false;
             }
+            if (cols[c].is_bool || cols[c].logical) {
+                if (!check_parquet_declared(fd.path, cols[c], sf.meta,
+                                            leaf[c]))
+                    return false;
+                continue;
+            }
             if ((int)sf.meta.phys_types.size() > leaf[c] &&
                 sf.meta.phys_types[leaf[c]] != expected_phys(cols[c].dtype)) {
                 set_error("%s: column %s physical type %d does not match "
@@ -2199,7 +2582,10 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     if (cc.codec != CODEC_ZSTD || cc.pages.empty()) continue;
                     if (zchunk_base.count(&cc)) continue;
                     zchunk_base[&cc] = out;
-                    bool needs_host = cols[c].dtype == PMH_DT_STRING;
+                    // boolean pages are bit-packed: staging walks them on
+                    // the host, they never stage as PLAIN column bytes
+                    bool needs_host =
+                        cols[c].dtype == PMH_DT_STRING || cols[c].is_bool;
                     const bool has_def =
                         sf.meta.max_def_levels[leaf[c]] > 0;
                     int64_t c0 = out;
@@ -2377,6 +2763,9 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                 int64_t dict_count = 0;
                 for (size_t pi = 0; pi < cc.pages.size(); pi++) {
                     auto &pg = cc.pages[pi];
+                    if (cols[c].is_bool &&
+                        !check_bool_page(fd.path, cols[c], pg))
+                        return false;
                     if (pg.page_type == 2) {
                         dict_host = payload_base + ppo[pi];
                         dict_count = pg.num_values;
@@ -2438,7 +2827,67 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     }
                     vpos[pi] = pos;
                 }
-                if (has_dba) {
+                if (cols[c].is_bool) {
+                    // PLAIN booleans: 1 bit per value, LSB first, every page
+                    // restarting on a byte boundary. The payload image
+                    // uploads verbatim (+16 B pad, the staging convention);
+                    // k_bits_expand materialises the column at read time,
+                    // into the dense buffer where the chunk has nulls
+                    // (k_level_scatter positions them, as for DELTA)
+                    int64_t payload_len = 0;
+                    for (size_t pi = 0; pi < cc.pages.size(); pi++)
+                        payload_len = std::max(
+                            payload_len,
+                            ppo[pi] + (cc.codec != CODEC_UNCOMPRESSED
+                                           ? cc.pages[pi].uncompressed_size
+                                           : cc.pages[pi].compressed_size));
+                    void *dev = plan->bufs.alloc(payload_len + 16);
+                    if (!dev) return false;
+                    if (payload_len &&
+                        hipMemcpy(dev, payload_base, payload_len,
+                                  hipMemcpyHostToDevice) != hipSuccess) {
+                        set_error("H2D failed");
+                        return false;
+                    }
+                    plan->encoded_bytes_total += payload_len;
+                    if (chunk_nulls) rc.has_nulls = true;
+                    for (size_t pi = 0; pi < cc.pages.size(); pi++) {
+                        auto &pg = cc.pages[pi];
+                        if (pg.page_type != 0) continue;
+                        const uint8_t *pp = payload_base + ppo[pi];
+                        const int64_t pos = vpos[pi];
+                        const int64_t plen = (cc.codec != CODEC_UNCOMPRESSED
+                                                  ? pg.uncompressed_size
+                                                  : pg.compressed_size);
+                        int64_t n_vals = pg.num_values;
+                        int64_t out0 = chunk_row0 + pg.first_row;
+                        int target = 0;
+                        if (chunk_nulls && max_def > 0) {
+                            uint32_t dl_len;
+                            memcpy(&dl_len, pp, 4);
+                            int64_t rel = (int64_t)rc.levels_host.size();
+                            rc.levels_host.insert(rc.levels_host.end(),
+                                                  pp + 4, pp + 4 + dl_len);
+                            int64_t before = rc.dense_before;
+                            if (!prescan_def(pp + 4, dl_len, pg.num_values,
+                                             out0, rel, &rc.dense_before,
+                                             rc.def_host))
+                                return false;
+                            n_vals = rc.dense_before - before;
+                            out0 = before;
+                            target = 1;
+                        }
+                        const char *why = "";
+                        if (!prescan_bits_plain(
+                                pp + pos, plen - pos, n_vals, stored, target,
+                                (uint64_t)dev + (uint64_t)(ppo[pi] + pos),
+                                out0, rc.bits_host, &why)) {
+                            set_error("%s col %s: %s", fd.path.c_str(),
+                                      cols[c].name.c_str(), why);
+                            return false;
+                        }
+                    }
+                } else if (has_dba) {
                     // DELTA_BYTE_ARRAY strings (VectorizedDeltaByteArray-
                     // Reader.java): per page, prefix lengths (DELTA) +
                     // suffix lengths (DELTA) + suffix bytes; values share
@@ -2876,10 +3325,24 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                 (int32_t *)plan->bufs.alloc((size_t)rc.scale_rows * 4);
             if (!rc.scale_dev) return false;
         }
+        if (rc.nanos_rows) {
+            rc.nanos_dev =
+                (uint64_t *)plan->bufs.alloc((size_t)rc.nanos_rows * 8);
+            if (!rc.nanos_dev) return false;
+        }
         for (auto &vc : rc.rlev2_host)
-            vc.out_addr = vc.dense_target == 2 ? (uint64_t)rc.scale_dev
-                          : vc.dense_target    ? (uint64_t)rc.dense_dev
-                                               : (uint64_t)rc.contig;
+            vc.out_addr = vc.dense_target == 3   ? (uint64_t)rc.nanos_dev
+                          : vc.dense_target == 2 ? (uint64_t)rc.scale_dev
+                          : vc.dense_target      ? (uint64_t)rc.dense_dev
+                                                 : (uint64_t)rc.contig;
+        for (auto &bu : rc.bits_host)
+            bu.out_addr =
+                bu.dense_target ? (uint64_t)rc.dense_dev : (uint64_t)rc.contig;
+        for (auto &tu : rc.ts_host) {
+            tu.out_addr =
+                tu.dense_target ? (uint64_t)rc.dense_dev : (uint64_t)rc.contig;
+            tu.nanos_addr = (uint64_t)rc.nanos_dev;
+        }
         for (auto &vu : rc.varint_host) {
             vu.out_addr =
                 vu.dense_target ? (uint64_t)rc.dense_dev : (uint64_t)rc.contig;
@@ -3238,6 +3701,8 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
     };
     std::vector<Rlev2Chunk> all_v;
     std::vector<VarintUnit> all_u;
+    std::vector<BitsUnit> all_b;
+    std::vector<TsUnit> all_t;
     std::vector<RleChunk> all_d;
     std::vector<DeltaChunk> all_dc;
     std::vector<DeltaStream> all_ds;
@@ -3247,8 +3712,12 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
             sec.any_decode |= rc.dict_encoded || rc.has_nulls ||
                               !rc.rlev2_host.empty() ||
                               !rc.varint_host.empty() ||
+                              !rc.bits_host.empty() ||
                               !rc.delta_host.empty() ||
                               !rc.gathers.empty();
+            all_b.insert(all_b.end(), rc.bits_host.begin(),
+                         rc.bits_host.end());
+            all_t.insert(all_t.end(), rc.ts_host.begin(), rc.ts_host.end());
             all_v.insert(all_v.end(), rc.rlev2_host.begin(),
                          rc.rlev2_host.end());
             all_u.insert(all_u.end(), rc.varint_host.begin(),
@@ -3269,6 +3738,25 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
         sec.rlev2_all =
             (Rlev2Chunk *)up(all_v.data(), all_v.size() * sizeof(Rlev2Chunk));
         if (!sec.rlev2_all) return false;
+    }
+    sec.n_bits = (int64_t)all_b.size();
+    if (sec.n_bits) {
+        sec.bits_all =
+            (BitsUnit *)up(all_b.data(), all_b.size() * sizeof(BitsUnit));
+        if (!sec.bits_all) return false;
+    }
+    sec.n_ts = (int64_t)all_t.size();
+    if (sec.n_ts) {
+        // timestamp refusals land in the section's error word, like the
+        // decimal ones below
+        if (!sec.err_dev) {
+            sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
+            if (!sec.err_dev || hipMemset(sec.err_dev, 0, 4) != hipSuccess)
+                return false;
+        }
+        for (auto &tu : all_t) tu.err_addr = (uint64_t)sec.err_dev;
+        sec.ts_all = (TsUnit *)up(all_t.data(), all_t.size() * sizeof(TsUnit));
+        if (!sec.ts_all) return false;
     }
     sec.n_varint = (int64_t)all_u.size();
     if (sec.n_varint) {
@@ -3325,6 +3813,23 @@ static hipError_t launch_section_decode(pmh_plan_t *p, Section &sec,
                 pmh_launch_orc_varint(sec.varint_all, sec.n_varint, st);
             if (e != hipSuccess) {
                 *what = "orc_varint";
+                return e;
+            }
+        }
+        if (sec.n_ts) {
+            // after k_rlev2 on the same stream: it decodes the seconds to
+            // the column and the stored nanos to the scratch
+            hipError_t e =
+                pmh_launch_orc_timestamp(sec.ts_all, sec.n_ts, st);
+            if (e != hipSuccess) {
+                *what = "orc_timestamp";
+                return e;
+            }
+        }
+        if (sec.n_bits) {
+            hipError_t e = pmh_launch_bits_expand(sec.bits_all, sec.n_bits, st);
+            if (e != hipSuccess) {
+                *what = "bits_expand";
                 return e;
             }
         }
@@ -3446,7 +3951,9 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 cs.precision = dp;
                 cs.scale = ds;
             } else {
-                cs.dtype = dtype_from_str(ts);
+                const int bt = parse_bool_or_temporal(ts, cs);
+                if (bt < 0) return false;
+                if (bt == 0) cs.dtype = dtype_from_str(ts);
             }
             if (cs.dtype < 0 || cs.name.empty()) {
                 set_error("bad column spec");
@@ -3467,6 +3974,21 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
         {
             int shift = 64;
             for (size_t i = 0; i < kc.arr.size(); i++) {
+                {
+                    ColSpec probe;
+                    const std::string kts = kc.arr[i]["type"].as_str();
+                    const int bt = parse_bool_or_temporal(kts, probe);
+                    if (bt < 0) return nullptr;
+                    if (bt > 0) {
+                        set_error("key column '%s': a %s key column is a "
+                                  "later round (boolean / date / time / "
+                                  "timestamp are value-column and "
+                                  "sequence-field types in v1)",
+                                  kc.arr[i]["name"].as_str().c_str(),
+                                  kts.c_str());
+                        return nullptr;
+                    }
+                }
                 int dt = dtype_from_str(kc.arr[i]["type"].as_str());
                 if (dt < PMH_DT_INT8 || dt > PMH_DT_INT64) {
                     set_error("key column %zu: integer types only "
@@ -3926,14 +4448,19 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                           hipGetErrorString(de));
                 return nullptr;
             }
-            if (ls.n_varint) {
+            if (ls.n_varint || ls.n_ts) {
                 uint32_t ew = 0;
                 if (hipMemcpy(&ew, ls.err_dev, 4, hipMemcpyDeviceToHost) !=
                     hipSuccess) {
                     set_error("lookup levels: err D2H failed");
                     return nullptr;
                 }
-                if (ew >> ODC_ERR_SHIFT) {
+                if (ew >> OTS_ERR_SHIFT) {
+                    set_error("lookup levels: %s",
+                              orc_timestamp_error(ew).c_str());
+                    return nullptr;
+                }
+                if (orc_decimal_bits(ew)) {
                     set_error("lookup levels: %s",
                               orc_decimal_error(ew).c_str());
                     return nullptr;
@@ -4128,6 +4655,19 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                     set_error("aggregate '%s' on a string column is not on "
                               "the GPU path (ids are not ordered by value)",
                               kv.second.as_str().c_str());
+                    return nullptr;
+                }
+                if ((plan->cols[idx].is_bool || plan->cols[idx].logical) &&
+                    code == PMH_AGG_SUM) {
+                    set_error("aggregate 'sum' on %s column '%s' is not "
+                              "supported (boolean / date / time / timestamp "
+                              "columns take last_value, first_value, "
+                              "last_non_null_value, first_non_null_value, "
+                              "max, min)",
+                              plan->cols[idx].is_bool
+                                  ? "boolean"
+                                  : logical_name(plan->cols[idx].logical),
+                              kv.first.c_str());
                     return nullptr;
                 }
                 if (plan->rrod && (code == PMH_AGG_FIRST_VALUE ||
@@ -4508,7 +5048,11 @@ collect:
                   "predecessor tile");
         return -1;
     }
-    if (err_word >> ODC_ERR_SHIFT) {
+    if (err_word >> OTS_ERR_SHIFT) {
+        set_error("%s", orc_timestamp_error(err_word).c_str());
+        return -1;
+    }
+    if (orc_decimal_bits(err_word)) {
         set_error("%s", orc_decimal_error(err_word).c_str());
         return -1;
     }
@@ -4573,7 +5117,8 @@ collect:
     for (int c = 0; c < n_cols; c++) {
         pmh_col &pc = p->batch_cols[c];
         pc.name = p->col_names[c].c_str();
-        pc.dtype = p->cols[c].dtype;
+        pc.dtype = p->cols[c].is_bool ? PMH_DT_BOOL : p->cols[c].dtype;
+        pc.logical = p->cols[c].logical;
         pc.data = p->host_output ? (const void *)p->out_host[c].data()
                                  : (const void *)p->out_dev[c];
         pc.valid = nullptr;
@@ -4995,7 +5540,7 @@ int64_t pmh_debug_orc_decimal(const void *data, int64_t len,
                 break;
             }
         memcpy(out, back.data() + g, (size_t)n_values * out_esize);
-        if (rc >= 0 && (err_word >> ODC_ERR_SHIFT)) {
+        if (rc >= 0 && orc_decimal_bits(err_word)) {
             set_error("pmh_debug_orc_decimal: %s",
                       orc_decimal_error(err_word).c_str());
             rc = -1;
@@ -5005,6 +5550,284 @@ int64_t pmh_debug_orc_decimal(const void *data, int64_t len,
     if (d_out) (void)hipFree(d_out);
     if (d_scales) (void)hipFree(d_scales);
     if (d_err) (void)hipFree(d_err);
+    if (d_units) (void)hipFree(d_units);
+    return rc;
+}
+
+// Stream-level entry to the BOOLEAN decode (the two prescans, the shared
+// scalar core, k_bits_expand): see paimon_hip.h. Calls the very functions
+// the plan calls.
+int64_t pmh_debug_bits(const void *stream, int64_t len, int64_t n_values,
+                       int bit_order, int format, int out_esize, int mode,
+                       int64_t src_shift, int64_t out_shift, void *out,
+                       int64_t out_cap) {
+    const uint8_t *s = (const uint8_t *)stream;
+    if ((!s && len > 0) || len < 0 || n_values < 0 ||
+        (bit_order != BITS_LSB && bit_order != BITS_MSB) ||
+        (format != 0 && format != 1) || (out_esize != 1 && out_esize != 4) ||
+        (mode != 0 && mode != 2) || src_shift < 0 || src_shift > 7 ||
+        out_shift < 0 || out_shift > 7 || out_cap < n_values ||
+        (n_values > 0 && !out)) {
+        set_error("pmh_debug_bits: bad arguments (bit_order 0|1, format 0|1, "
+                  "out_esize 1|4, mode 0|2, src_shift 0..7, out_shift 0..7, "
+                  "out_cap >= n_values >= 0)");
+        return -1;
+    }
+    if (n_values == 0) return 0;
+    std::vector<BitsUnit> units;
+    auto prescan = [&](uint64_t dev_base) {
+        const char *why = "";
+        units.clear();
+        const bool ok =
+            format == 0 ? prescan_bits_plain(s, len, n_values, out_esize, 0,
+                                             dev_base, 0, units, &why)
+                        : prescan_boolrle(s, len, n_values, out_esize, 0,
+                                          dev_base, 0, units, &why);
+        if (!ok) set_error("pmh_debug_bits: %s", why);
+        for (auto &u : units) u.msb = (uint8_t)bit_order;
+        return ok;
+    };
+    if (mode == 0) {  // host twin: src offsets relative to the stream
+        if (!prescan(0)) return -1;
+        for (auto &u : units) {
+            // pose the requested alignment: element 0 sits out_shift
+            // elements past an address aligned to 8 elements
+            u.out_addr = (uint64_t)out_shift * (uint64_t)out_esize;
+            bits_decode_unit_host(s + u.src, u, out);
+        }
+        return n_values;
+    }
+    // device path: stream at an 8-byte-aligned address + src_shift with the
+    // 16-byte tail pad staging gives it; output out_shift elements past an
+    // address aligned to 8 elements, between two guard zones
+    const int64_t GUARD = 64;  // elements, each side (a multiple of 8)
+    const uint8_t FILL = 0xA5;
+    uint8_t *d_src = nullptr, *d_out = nullptr;
+    BitsUnit *d_units = nullptr;
+    const size_t lead = (size_t)(GUARD + out_shift) * out_esize;
+    const size_t body = (size_t)n_values * out_esize;
+    const size_t out_bytes = lead + body + (size_t)GUARD * out_esize;
+    std::vector<uint8_t> back(out_bytes);
+    int64_t rc = -1;
+    do {
+        if (hipMalloc(&d_src, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMalloc(&d_out, out_bytes) != hipSuccess) {
+            set_error("pmh_debug_bits: hipMalloc failed");
+            break;
+        }
+        if (((uint64_t)d_src & 7) != 0 || ((uint64_t)d_out & 31) != 0) {
+            set_error("pmh_debug_bits: device allocation not aligned");
+            break;
+        }
+        if (hipMemset(d_src, 0, (size_t)len + 8 + 16) != hipSuccess ||
+            hipMemset(d_out, FILL, out_bytes) != hipSuccess ||
+            (len && hipMemcpy(d_src + src_shift, s, (size_t)len,
+                              hipMemcpyHostToDevice) != hipSuccess)) {
+            set_error("pmh_debug_bits: H2D failed");
+            break;
+        }
+        if (!prescan((uint64_t)(d_src + src_shift))) break;
+        for (auto &u : units) u.out_addr = (uint64_t)(d_out + lead);
+        if (hipMalloc(&d_units, units.size() * sizeof(BitsUnit)) !=
+                hipSuccess ||
+            hipMemcpy(d_units, units.data(), units.size() * sizeof(BitsUnit),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("pmh_debug_bits: unit upload failed");
+            break;
+        }
+        hipError_t e =
+            pmh_launch_bits_expand(d_units, (int64_t)units.size(), nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess)
+            e = hipMemcpy(back.data(), d_out, out_bytes,
+                          hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_error("pmh_debug_bits: k_bits_expand: %s",
+                      hipGetErrorString(e));
+            break;
+        }
+        rc = n_values;
+        for (size_t i = 0; i < out_bytes; i++) {
+            if (i >= lead && i < lead + body) continue;
+            if (back[i] != FILL) {
+                set_error("pmh_debug_bits: k_bits_expand wrote outside its "
+                          "output (guard zone changed)");
+                rc = -2;
+                break;
+            }
+        }
+        memcpy(out, back.data() + lead, body);
+    } while (0);
+    if (d_src) (void)hipFree(d_src);
+    if (d_out) (void)hipFree(d_out);
+    if (d_units) (void)hipFree(d_units);
+    return rc;
+}
+
+// Stream-level entry to the ORC TIMESTAMP decode (prescan_rlev2 + k_rlev2
+// for both streams, the shared scalar core, k_orc_timestamp): see
+// paimon_hip.h.
+int64_t pmh_debug_orc_timestamp(const void *data, int64_t data_len,
+                                const void *secondary, int64_t secondary_len,
+                                int64_t n_values, int unit, int mode,
+                                void *out, int64_t out_cap) {
+    const uint8_t *ds = (const uint8_t *)data;
+    const uint8_t *ss = (const uint8_t *)secondary;
+    if ((!ds && data_len > 0) || (!ss && secondary_len > 0) || data_len < 0 ||
+        secondary_len < 0 || n_values < 0 ||
+        (unit != OTS_UNIT_MILLIS && unit != OTS_UNIT_MICROS) ||
+        (mode != 0 && mode != 2) || out_cap < n_values ||
+        (n_values > 0 && !out)) {
+        set_error("pmh_debug_orc_timestamp: bad arguments (unit 0|1, mode "
+                  "0|2, out_cap >= n_values >= 0)");
+        return -1;
+    }
+    if (n_values == 0) return 0;
+    // both streams have to hold exactly n_values: the plan sizes the column
+    // and the nanos scratch by the row count
+    std::vector<Rlev2Chunk> dch, sch;
+    auto prescan = [&](uint64_t d_base, uint64_t s_base) {
+        dch.clear();
+        sch.clear();
+        if (!prescan_rlev2(ds, data_len, n_values, 1, 8, 0, d_base, 0, dch) ||
+            !prescan_rlev2(ss, secondary_len, n_values, 0, 8, 3, s_base, 0,
+                           sch)) {
+            const std::string why = last_error();
+            set_error("pmh_debug_orc_timestamp: %s", why.c_str());
+            return false;
+        }
+        int64_t d_end = 0, s_end = 0;
+        for (const auto &k : dch) d_end = k.out_start + k.count;
+        for (const auto &k : sch) s_end = k.out_start + k.count;
+        if (d_end != n_values || s_end != n_values) {
+            set_error("pmh_debug_orc_timestamp: streams hold %lld seconds "
+                      "and %lld nanos for %lld values", (long long)d_end,
+                      (long long)s_end, (long long)n_values);
+            return false;
+        }
+        return true;
+    };
+    if (mode == 0) {  // host: the oracle-independent host RLEv2 + the core
+        if (!prescan(0x1000, 0x1000)) return -1;
+        std::vector<uint64_t> secs_zz, nanos;
+        if (!host_rlev2_s(ds, data_len, n_values, secs_zz) ||
+            !host_rlev2_u(ss, secondary_len, n_values, nanos) ||
+            (int64_t)secs_zz.size() < n_values ||
+            (int64_t)nanos.size() < n_values) {
+            set_error("pmh_debug_orc_timestamp: host RLEv2 decode failed");
+            return -1;
+        }
+        for (int64_t i = 0; i < n_values; i++) {
+            int64_t v;
+            const int err =
+                ots_value((int64_t)secs_zz[i], nanos[i], unit, &v);
+            if (err) {
+                set_error("pmh_debug_orc_timestamp: ORC timestamp refused "
+                          "at value %lld: %s", (long long)i,
+                          ots_err_text(err));
+                return -1;
+            }
+            ((int64_t *)out)[i] = v;
+        }
+        return n_values;
+    }
+    const int64_t GUARD = 64;  // elements, each side
+    const uint8_t FILL = 0xA5;
+    uint8_t *d_data = nullptr, *d_sec = nullptr, *d_out = nullptr;
+    uint64_t *d_nanos = nullptr;
+    uint32_t *d_err = nullptr;
+    Rlev2Chunk *d_chunks = nullptr;
+    TsUnit *d_units = nullptr;
+    const size_t out_bytes = (size_t)(n_values + 2 * GUARD) * 8;
+    std::vector<uint8_t> back(out_bytes);
+    int64_t rc = -1;
+    do {
+        if (hipMalloc(&d_data, (size_t)data_len + 16) != hipSuccess ||
+            hipMalloc(&d_sec, (size_t)secondary_len + 16) != hipSuccess ||
+            hipMalloc(&d_out, out_bytes) != hipSuccess ||
+            hipMalloc(&d_nanos, (size_t)n_values * 8) != hipSuccess ||
+            hipMalloc(&d_err, 4) != hipSuccess) {
+            set_error("pmh_debug_orc_timestamp: hipMalloc failed");
+            break;
+        }
+        if (hipMemset(d_data, 0, (size_t)data_len + 16) != hipSuccess ||
+            hipMemset(d_sec, 0, (size_t)secondary_len + 16) != hipSuccess ||
+            hipMemset(d_out, FILL, out_bytes) != hipSuccess ||
+            hipMemset(d_nanos, FILL, (size_t)n_values * 8) != hipSuccess ||
+            hipMemset(d_err, 0, 4) != hipSuccess ||
+            (data_len && hipMemcpy(d_data, ds, (size_t)data_len,
+                                   hipMemcpyHostToDevice) != hipSuccess) ||
+            (secondary_len &&
+             hipMemcpy(d_sec, ss, (size_t)secondary_len,
+                       hipMemcpyHostToDevice) != hipSuccess)) {
+            set_error("pmh_debug_orc_timestamp: H2D failed");
+            break;
+        }
+        if (!prescan((uint64_t)d_data, (uint64_t)d_sec)) break;
+        for (auto &k : dch) k.out_addr = (uint64_t)(d_out + GUARD * 8);
+        for (auto &k : sch) k.out_addr = (uint64_t)d_nanos;
+        dch.insert(dch.end(), sch.begin(), sch.end());
+        std::vector<TsUnit> units;
+        for (int64_t d = 0; d < n_values; d += OTS_UNIT_VALUES) {
+            TsUnit tu{};
+            tu.out_addr = (uint64_t)(d_out + GUARD * 8);
+            tu.nanos_addr = (uint64_t)d_nanos;
+            tu.err_addr = (uint64_t)d_err;
+            tu.out_start = d;
+            tu.nanos_start = d;
+            tu.count =
+                (int32_t)std::min<int64_t>(OTS_UNIT_VALUES, n_values - d);
+            tu.unit = (uint8_t)unit;
+            units.push_back(tu);
+        }
+        if (hipMalloc(&d_chunks, dch.size() * sizeof(Rlev2Chunk)) !=
+                hipSuccess ||
+            hipMalloc(&d_units, units.size() * sizeof(TsUnit)) != hipSuccess ||
+            hipMemcpy(d_chunks, dch.data(), dch.size() * sizeof(Rlev2Chunk),
+                      hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_units, units.data(), units.size() * sizeof(TsUnit),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("pmh_debug_orc_timestamp: work upload failed");
+            break;
+        }
+        uint32_t err_word = 0;
+        hipError_t e = pmh_launch_rlev2(d_chunks, (int64_t)dch.size(), nullptr);
+        if (e == hipSuccess)
+            e = pmh_launch_orc_timestamp(d_units, (int64_t)units.size(),
+                                         nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess)
+            e = hipMemcpy(back.data(), d_out, out_bytes,
+                          hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(&err_word, d_err, 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_error("pmh_debug_orc_timestamp: k_rlev2 / k_orc_timestamp: "
+                      "%s", hipGetErrorString(e));
+            break;
+        }
+        rc = n_values;
+        const size_t g = (size_t)GUARD * 8;
+        for (size_t i = 0; i < g; i++)
+            if (back[i] != FILL || back[out_bytes - 1 - i] != FILL) {
+                set_error("pmh_debug_orc_timestamp: a kernel wrote outside "
+                          "its output (guard zone changed)");
+                rc = -2;
+                break;
+            }
+        memcpy(out, back.data() + g, (size_t)n_values * 8);
+        if (rc >= 0 && (err_word >> OTS_ERR_SHIFT)) {
+            set_error("pmh_debug_orc_timestamp: %s",
+                      orc_timestamp_error(err_word).c_str());
+            rc = -1;
+        }
+    } while (0);
+    if (d_data) (void)hipFree(d_data);
+    if (d_sec) (void)hipFree(d_sec);
+    if (d_out) (void)hipFree(d_out);
+    if (d_nanos) (void)hipFree(d_nanos);
+    if (d_err) (void)hipFree(d_err);
+    if (d_chunks) (void)hipFree(d_chunks);
     if (d_units) (void)hipFree(d_units);
     return rc;
 }
@@ -5048,6 +5871,7 @@ int pmh_write_parquet(const pmh_col *cols, int32_t n_cols, int64_t n_rows,
         pc[i].dict_len = cols[i].dict_len;
         pc[i].precision = cols[i].precision;
         pc[i].scale = cols[i].scale;
+        pc[i].logical = cols[i].logical;
         if (pc[i].name.empty() || (!pc[i].data && n_rows > 0)) {
             set_error("pmh_write_parquet: column %d missing name/data", i);
             return -1;
@@ -5071,7 +5895,13 @@ char *pmh_debug_footer_json(const char *path) {
         if (i) out += ",";
         out += "{\"name\": \"" + json_escape(sf.meta.schema_names[i]) +
                "\", \"max_def\": " + std::to_string(sf.meta.max_def_levels[i]) +
-               ", \"phys\": " + std::to_string(sf.meta.phys_types[i]) + "}";
+               ", \"phys\": " + std::to_string(sf.meta.phys_types[i]) +
+               ", \"converted\": " +
+               std::to_string(sf.meta.converted_types[i]) +
+               ", \"logical\": " + std::to_string(sf.meta.logical_kinds[i]) +
+               ", \"unit\": \"" + pq_unit_name(sf.meta.logical_units[i]) +
+               "\", \"utc\": " + (sf.meta.logical_utc[i] ? "true" : "false") +
+               "}";
     }
     out += "], \"row_groups\": [";
     for (size_t g = 0; g < sf.meta.row_groups.size(); g++) {
@@ -5097,6 +5927,63 @@ char *pmh_debug_footer_json(const char *path) {
     }
     out += "]}";
     return strdup(out.c_str());
+}
+
+// The file-against-declared-type checks of staging, without a plan or a GPU:
+// see paimon_hip.h. Calls the very functions staging calls.
+int pmh_debug_check_column(const char *path, const char *column,
+                           const char *type) {
+    if (!path || !column || !type) {
+        set_error("pmh_debug_check_column: bad arguments");
+        return -1;
+    }
+    ColSpec cs;
+    cs.name = column;
+    cs.dtype = -1;
+    int dp = 0, ds = 0;
+    const std::string ts = type;
+    if (parse_decimal(ts, &dp, &ds)) {
+        cs.dtype = dp <= 9 ? PMH_DT_INT32 : PMH_DT_INT64;
+        cs.precision = dp;
+        cs.scale = ds;
+    } else {
+        const int bt = parse_bool_or_temporal(ts, cs);
+        if (bt < 0) return -1;
+        if (bt == 0) cs.dtype = dtype_from_str(ts);
+    }
+    if (cs.dtype < 0) {
+        set_error("pmh_debug_check_column: unknown type '%s'", type);
+        return -1;
+    }
+    StagedFile sf;
+    if (!load_file(path, sf)) return -1;
+    if (sf.orc) {
+        const OrcFileMeta &om = sf.orc_meta;
+        int cid = -1;
+        for (size_t i = 0; i < om.column_names.size(); i++)
+            if (om.column_names[i] == cs.name) cid = (int)i + 1;
+        if (cid < 0) {
+            set_error("%s: column %s not found", path, column);
+            return -1;
+        }
+        for (const auto &st : om.stripes)
+            if (!check_orc_declared(path, cs, om.column_kinds[cid - 1], st))
+                return -1;
+        return 0;
+    }
+    int leaf = -1;
+    for (size_t i = 0; i < sf.meta.schema_names.size(); i++)
+        if (sf.meta.schema_names[i] == cs.name) leaf = (int)i;
+    if (leaf < 0) {
+        set_error("%s: column %s not found", path, column);
+        return -1;
+    }
+    if (!check_parquet_declared(path, cs, sf.meta, leaf)) return -1;
+    if (cs.is_bool)
+        for (const auto &rg : sf.meta.row_groups)
+            for (const auto &pg : rg.columns[leaf].pages)
+                if (!check_bool_page(path, cs, pg)) return -1;
+    return 0;
 }
 
 // Host entry to the lookup search core (lookup_core.h) shared with

@@ -26,7 +26,15 @@ LIB_PATH = os.path.join(_HERE, "libpaimon_hip.so")
 
 _DT_NP = {1: np.int8, 2: np.int16, 3: np.int32, 4: np.int64,
           5: np.float32, 6: np.float64,
-          7: np.int32}  # PMH_DT_STRING: global-dictionary ids
+          7: np.int32,  # PMH_DT_STRING: global-dictionary ids
+          8: np.bool_}  # PMH_DT_BOOL: one 0/1 byte per row
+
+# enum pmh_logical: the annotation of an INT32/INT64 column. Values are
+# handed out as the plain integers (days, milliseconds of the day,
+# milliseconds / microseconds since the epoch); nothing converts to datetime
+# on the read path.
+(LT_NONE, LT_DATE, LT_TIME_MILLIS, LT_TIMESTAMP_MILLIS, LT_TIMESTAMP_MICROS,
+ LT_TIMESTAMP_LTZ_MILLIS, LT_TIMESTAMP_LTZ_MICROS) = range(7)
 
 
 class _Col(ctypes.Structure):
@@ -35,7 +43,8 @@ class _Col(ctypes.Structure):
                 ("dict_data", ctypes.c_void_p),
                 ("dict_offsets", ctypes.POINTER(ctypes.c_int32)),
                 ("dict_len", ctypes.c_int32),
-                ("precision", ctypes.c_int32), ("scale", ctypes.c_int32)]
+                ("precision", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("logical", ctypes.c_int32)]
 
 
 class _Batch(ctypes.Structure):
@@ -132,11 +141,13 @@ def debug_footer(path):
 
 _NP_DT = {np.dtype(np.int8): 1, np.dtype(np.int16): 2,
           np.dtype(np.int32): 3, np.dtype(np.int64): 4,
-          np.dtype(np.float32): 5, np.dtype(np.float64): 6}
+          np.dtype(np.float32): 5, np.dtype(np.float64): 6,
+          np.dtype(np.bool_): 8}
 
 
 def write_parquet(path, columns, row_group_rows=0, page_rows=0,
-                  compression="NONE", dicts=None, decimals=None):
+                  compression="NONE", dicts=None, decimals=None,
+                  logicals=None):
     """Write a Parquet v1 data file via the native writer
     (pmh_write_parquet) — the compaction write-back path. `columns` is an
     ordered list of (name, values[, valid]) with numpy arrays; valid
@@ -148,10 +159,14 @@ def write_parquet(path, columns, row_group_rows=0, page_rows=0,
     default for strings).
     decimals: {name: (precision, scale)} — int32/int64 unscaled values
     written with the DECIMAL annotation (INT32 p<=9 / INT64 p<=18,
-    ParquetSchemaConverter.java:153-171)."""
+    ParquetSchemaConverter.java:153-171).
+    logicals: {name: LT_*} — int32 (date, time) / int64 (timestamp) values
+    written with that annotation. numpy bool columns are written as BOOLEAN,
+    bit-packed."""
     lib = load_lib()
     dicts = dicts or {}
     decimals = decimals or {}
+    logicals = logicals or {}
     n_rows = len(columns[0][1]) if columns else 0
     arrs = []  # keep contiguous buffers alive
     cols = (_Col * len(columns))()
@@ -186,6 +201,8 @@ def write_parquet(path, columns, row_group_rows=0, page_rows=0,
             p, s = decimals[name]
             cols[i].precision = int(p)
             cols[i].scale = int(s)
+        elif logicals.get(name):
+            cols[i].logical = int(logicals[name])
         if valid is not None:
             v8 = np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
             if len(v8) != n_rows:
@@ -363,6 +380,86 @@ def debug_orc_decimal(data, n_values, precision, scale, mode, scales=None,
     return out[:n_values]
 
 
+BITS_LSB, BITS_MSB = 0, 1          # bit order inside a byte
+BITS_RAW, BITS_BYTE_RLE = 0, 1     # Parquet PLAIN bits / ORC boolean RLE
+BITS_HOST, BITS_DEVICE = 0, 2
+
+
+def debug_bits(stream, n_values, bit_order, fmt, mode, out_esize=1,
+               src_shift=0, out_shift=0):
+    """One BOOLEAN value stream through the product's decoder
+    (pmh_debug_bits): raw LSB/MSB-first bits (a Parquet PLAIN page payload)
+    or an ORC boolean byte-RLE stream. BITS_HOST runs the prescan and the
+    scalar core on the host; BITS_DEVICE returns what k_bits_expand wrote
+    (needs a GPU), the output starting out_shift elements past an aligned
+    address. Returns uint8 (out_esize 1) or int32 (out_esize 4) values,
+    untouched elements still 0xA5.. in device mode. Raises RuntimeError on a
+    rejected stream; a device store outside the output raises
+    AssertionError."""
+    lib = load_lib()
+    lib.pmh_debug_bits.restype = ctypes.c_int64
+    lib.pmh_debug_bits.argtypes = [
+        ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+    stream = bytes(stream)
+    out = np.full(max(n_values, 1), 0xA5A5A5A5 if out_esize == 4 else 0xA5,
+                  dtype=np.uint32 if out_esize == 4 else np.uint8)
+    n = lib.pmh_debug_bits(stream, len(stream), n_values, bit_order, fmt,
+                           out_esize, mode, src_shift, out_shift,
+                           out.ctypes.data_as(ctypes.c_void_p), len(out))
+    if n == -2:
+        raise AssertionError(last_error())
+    if n < 0:
+        raise RuntimeError(last_error())
+    out = out[:n_values]
+    return out.view(np.int32) if out_esize == 4 else out
+
+
+ORC_TS_MILLIS, ORC_TS_MICROS = 0, 1
+ORC_TS_HOST, ORC_TS_DEVICE = 0, 2
+
+
+def debug_orc_timestamp(data, secondary, n_values, unit, mode):
+    """One ORC TIMESTAMP stream pair (DATA: signed RLEv2 seconds relative
+    to 2015-01-01; SECONDARY: unsigned RLEv2 nanos with trailing zeros
+    removed) through the product's decoders (pmh_debug_orc_timestamp).
+    Returns int64 milliseconds or microseconds since the epoch by unit.
+    ORC_TS_HOST needs no GPU; ORC_TS_DEVICE runs k_rlev2 + k_orc_timestamp.
+    Raises RuntimeError on a rejected stream or a refused value; a device
+    store outside the output raises AssertionError."""
+    lib = load_lib()
+    lib.pmh_debug_orc_timestamp.restype = ctypes.c_int64
+    lib.pmh_debug_orc_timestamp.argtypes = [
+        ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64]
+    data, secondary = bytes(data), bytes(secondary)
+    out = np.empty(max(n_values, 1), dtype=np.int64)
+    n = lib.pmh_debug_orc_timestamp(
+        data, len(data), secondary, len(secondary), n_values, unit, mode,
+        out.ctypes.data_as(ctypes.c_void_p), len(out))
+    if n == -2:
+        raise AssertionError(last_error())
+    if n < 0:
+        raise RuntimeError(last_error())
+    return out[:n_values]
+
+
+def debug_check_column(path, column, type_str):
+    """Check one column of a Parquet / ORC data file against a declared
+    plan type the way staging does, without a plan or a GPU
+    (pmh_debug_check_column). Raises RuntimeError with the text plan
+    creation would fail with."""
+    lib = load_lib()
+    lib.pmh_debug_check_column.restype = ctypes.c_int
+    lib.pmh_debug_check_column.argtypes = [ctypes.c_char_p, ctypes.c_char_p,
+                                           ctypes.c_char_p]
+    if lib.pmh_debug_check_column(path.encode(), column.encode(),
+                                  type_str.encode()) != 0:
+        raise RuntimeError(last_error())
+
+
 def interval_partition(min_keys, max_keys):
     """Returns (section_id, run_id) per input file, per the IntervalPartition
     restatement in libpaimon_hip (plan.cpp)."""
@@ -491,6 +588,9 @@ class MergeReadPlan:
         if not self.h:
             raise RuntimeError(f"pmh_plan_create: {last_error()}")
         self.output = output
+        # name -> LT_* of the date / time / timestamp columns, as the batches
+        # report it (compaction hands it to the writer)
+        self.logicals = {}
 
     def read_next(self):
         """Returns dict name -> numpy array (host output mode), or a raw
@@ -516,6 +616,8 @@ class MergeReadPlan:
             else:
                 arr = np.empty(0, dtype=dt)
             out[name] = arr
+            if col.logical:
+                self.logicals[name] = int(col.logical)
             if col.dtype == 7 and col.dict_len > 0:
                 # dictionary string column: values are global ids; expose
                 # the dictionary as an object array of bytes
