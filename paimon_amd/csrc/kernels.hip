@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 #include "lookup_core.h"
@@ -311,6 +313,19 @@ __global__ void k_partition_refine(const DevCol *keys, const int64_t *lens,
 // segmented (seq, isAdd) argmax per group (groups have <= k records: one
 // per run — SortedRun invariant, SortedRun.java), apply Deduplicate +
 // wrapper + drop-delete rules, and emit packed winners per owned group.
+// Staging is flat (thread tid owns segment elements tid + s * 512, all of a
+// tile's loads issued together) and, where registers allow, pipelined: a
+// block's next tile is loaded into registers while this one is merged.
+
+// Per-tile segment setup. Double-buffered: the staging prefetch of a block's
+// next tile fills the other buffer while the current tile is merged.
+struct TileSetup {
+    int32_t segoff[PMH_MAX_RUNS + 1];  // entries past k hold mtotal
+    int32_t rowoff[PMH_MAX_RUNS];  // run row of segment element sx is
+                                   // sx + rowoff[run]
+    int32_t mtotal;                // extended element count
+    int32_t mreal;  // real element count (rank width of this tile)
+};
 
 struct TileSmem {
     int64_t skey[PMH_TILE_MAX];
@@ -323,14 +338,26 @@ struct TileSmem {
     uint16_t perm[2][PMH_TILE_MAX];
     uint8_t head[PMH_TILE_MAX];    // group head flags (merged order)
     int32_t wave_tot[2 * (PMH_TILE_THREADS / 64)];
-    int32_t segoff[PMH_MAX_RUNS + 1];
-    int32_t seglen[PMH_MAX_RUNS];  // extended (incl. extra) lengths
-    int32_t paircnt[PMH_MAX_RUNS + 1];
-    int64_t predkey;
+    TileSetup setup[2];
+    // per-run column bases, copied once per block (tomb 0 = no tombstones);
+    // one record per run, so a slot's four lookups share one LDS address
+    struct RunBase {
+        uint64_t key, seq, kind, tomb;
+    } rb[PMH_MAX_RUNS];
+    int64_t predkey;  // largest key before any run's first element
     int32_t haspred;
-    int32_t mtotal;    // extended element count
-    int32_t mreal;     // real element count (rank width of this tile)
-    int32_t nemit;
+};
+
+// One tile's staged elements in registers: thread tid owns segment elements
+// tid + s * PMH_TILE_THREADS. Filled by tile_prefetch, drained by tile_store.
+template <bool TOMBS>
+struct TileRegs {
+    int64_t key[PMH_TILE_ITER];
+    int64_t seq[PMH_TILE_ITER];
+    int32_t kind[PMH_TILE_ITER];
+    uint8_t tomb[TOMBS ? PMH_TILE_ITER : 1];  // deletion-vector bytes
+    int64_t pred;  // threads tid < k: key before run tid's first element,
+                   // if the run's cut is not 0
 };
 
 // stable 2-way co-rank: number of A elements among the first d outputs of
@@ -384,6 +411,147 @@ DEV int useq_cmp(const DevCol *cols, const uint8_t *col_dtype, int n_cols,
 // ps2_* packing); helper so call sites read uniformly
 DEV bool ps2m_isadd(int64_t w) { return w & 1; }
 
+// Load through a global-address-space pointer: a generic (flat) load would
+// also count on the LDS counter, and the first LDS wait of the merge would
+// then drain the whole prefetch.
+template <typename T>
+DEV T gload(uint64_t addr) {
+    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(
+        addr);
+}
+
+// Issue every global load of one tile's staging at once: the 2k cuts and
+// run lengths (block-uniform addresses; KM is the unrolled run bound, as in
+// k_partition_wave), then the predecessor keys and all key / seq / kind /
+// tombstone loads of this thread's slots, into registers. Nothing here
+// waits on element data, so the caller may run other work (the previous
+// tile's merge) before the registers go to LDS. The tile's segment setup goes
+// to `st`; the caller's next barrier publishes it. [S0, S0 + NS) is the slot
+// range: a caller short of registers stages a tile in two halves (the
+// first call writes the setup).
+template <int KM, bool TOMBS, int HS, int S0 = 0, int NS = PMH_TILE_ITER>
+DEV void tile_prefetch(const TileSmem &sm, TileSetup &st,
+                       const int32_t *__restrict__ cuts,
+                       const int64_t *__restrict__ lens, int64_t tile, int k,
+                       int kes, int tid, TileRegs<TOMBS> &rg) {
+    const int32_t *c0 = cuts + tile * k;
+    const int32_t *c1 = c0 + k;
+    int32_t a[KM], len[KM];
+    int32_t M = 0, Mreal = 0;
+#pragma unroll
+    for (int r = 0; r < KM; r++) {
+        const int rr = r < k ? r : 0;  // loads stay unconditional
+        const int32_t ar = c0[rr], br = c1[rr];
+        const int32_t ln = (int32_t)lens[rr];
+        // extended: +1 element per run when available
+        a[r] = ar;
+        len[r] = r < k ? (br - ar) + (br < ln ? 1 : 0) : 0;
+        Mreal += r < k ? br - ar : 0;
+        M += len[r];
+    }
+    // segment setup of the tile: thread r publishes run r's offsets
+    int32_t so = 0, my_so = 0, my_a = 0;
+    if constexpr (S0 == 0) {
+#pragma unroll
+        for (int r = 0; r < KM; r++) {
+            if (tid == r) {
+                my_so = so;
+                my_a = a[r];
+            }
+            so += len[r];
+        }
+        if (tid <= KM) st.segoff[tid] = tid < k ? my_so : M;
+        if (tid < k) st.rowoff[tid] = my_a - my_so;
+        if (tid == 0) {
+            st.mtotal = M;
+            st.mreal = Mreal;
+        }
+        rg.pred = 0;
+    }
+    if (M <= 0) return;  // block-uniform: no element, no valid address
+    // Slots go in fenced groups of HS (4, or 2 where registers are short),
+    // column by column within a group, so only one group's lookups and
+    // addresses are live at a time (registers); every load of the tile is
+    // still issued before anything waits on element data.
+#pragma unroll
+    for (int h = S0; h < S0 + NS; h += HS) {
+        // slot -> (run, row): the last run whose segment offset is <= e
+        // (that run is non-empty because e < M). Dead slots clamp to element
+        // M - 1, so every slot loads from a valid address and only the LDS
+        // store is guarded.
+        int32_t e[HS], rowd[HS];
+        int run[HS];
+#pragma unroll
+        for (int s = 0; s < HS; s++) {
+            const int32_t x = tid + (h + s) * PMH_TILE_THREADS;
+            e[s] = x < M ? x : M - 1;
+            rowd[s] = 0;
+            run[s] = 0;
+        }
+        int32_t off = 0;
+#pragma unroll
+        for (int r = 0; r < KM; r++) {
+#pragma unroll
+            for (int s = 0; s < HS; s++) {
+                const bool in = r < k && e[s] >= off;
+                run[s] = in ? r : run[s];
+                rowd[s] = in ? a[r] - off : rowd[s];
+            }
+            off += len[r];
+        }
+        uint32_t row[HS];  // unsigned: widens for free in the address
+#pragma unroll
+        for (int s = 0; s < HS; s++) row[s] = (uint32_t)(e[s] + rowd[s]);
+        // The key width is uniform: one hoisted branch, a whole batch per
+        // arm. Keys stay raw (a 4-byte key is widened when it goes to LDS):
+        // converting here would wait for the load inside the arm.
+        if (kes == 8) {
+#pragma unroll
+            for (int s = 0; s < HS; s++)
+                rg.key[h + s] = gload<int64_t>(sm.rb[run[s]].key +
+                                               (uint64_t)row[s] * 8);
+        } else {
+#pragma unroll
+            for (int s = 0; s < HS; s++)
+                rg.key[h + s] = (int64_t)gload<uint32_t>(
+                    sm.rb[run[s]].key + (uint64_t)row[s] * 4);
+        }
+#pragma unroll
+        for (int s = 0; s < HS; s++)
+            rg.seq[h + s] =
+                gload<int64_t>(sm.rb[run[s]].seq + (uint64_t)row[s] * 8);
+#pragma unroll
+        for (int s = 0; s < HS; s++)
+            rg.kind[h + s] =
+                gload<int32_t>(sm.rb[run[s]].kind + (uint64_t)row[s] * 4);
+        if constexpr (TOMBS) {
+            // a run without tombstones reads byte 1 of the row's kind
+            // instead: valid memory, and zero (row kinds are 0..3), i.e.
+            // "not deleted"
+#pragma unroll
+            for (int s = 0; s < HS; s++) {
+                const uint64_t t = sm.rb[run[s]].tomb;
+                rg.tomb[h + s] = gload<uint8_t>(
+                    t ? t + (uint64_t)row[s]
+                      : sm.rb[run[s]].kind + (uint64_t)row[s] * 4 + 1);
+            }
+        }
+        if (h == 0 && tid < 64) {
+            // Predecessor keys ride in wave 0 (a wave-uniform branch); a
+            // thread without one re-reads its first slot's key, so the load
+            // is unconditional.
+            const bool haspred = tid < k && my_a > 0;
+            const uint64_t pbase =
+                haspred ? sm.rb[tid & (PMH_MAX_RUNS - 1)].key
+                        : sm.rb[run[0]].key;
+            const uint64_t prow = haspred ? (uint32_t)(my_a - 1) : row[0];
+            rg.pred = kes == 8 ? gload<int64_t>(pbase + prow * 8)
+                               : (int64_t)gload<uint32_t>(pbase + prow * 4);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // PU=true: PartialUpdate mode — no winner reduction; emit every owned
 // group's member list (ascending (seq, isAdd) order within the group) for
 // the per-field overlay in k_emit_pu. v1 accepts INSERT-only streams (the
@@ -397,10 +565,12 @@ DEV bool ps2m_isadd(int64_t w) { return w & 1; }
 // applies LookupMergeFunction's level rules and reads k_lookup_probe's
 // per-row probe words; its own instantiation, so the other modes' code is
 // untouched.
-template <bool PU, bool FR, bool LK = false>
-__launch_bounds__(PMH_TILE_THREADS) __global__
+template <bool PU, bool FR, bool LK, int KM, bool TOMBS>
+__attribute__((amdgpu_waves_per_eu(4))) __launch_bounds__(PMH_TILE_THREADS, 2)
+__global__
 void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
-                   const int64_t *lens, int k, const int32_t *cuts,
+                   const int64_t *__restrict__ lens, int k,
+                   const int32_t *__restrict__ cuts,
                    int64_t n_tiles, int64_t tile_rows, int flags,
                    const uint64_t *tombs, uint32_t *winners,
                    int32_t *tile_counts, uint16_t *group_start,
@@ -442,93 +612,99 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
     // compiler cannot dead-code the ablated phases' inputs.
     const int ablate = (flags >> 8) & 0xf;
     __shared__ TileSmem sm;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        const int32_t *c0 = &cuts[tile * k];
-        const int32_t *c1 = &cuts[(tile + 1) * k];
-
-        // --- segment setup (extended: +1 element per run when available).
-        // Parallel across the first k threads — a serial tid-0 loop of ~30
-        // dependent global loads stalled the whole tile (ablation,
-        // profiles/r01_c2_pmc.md); only the tiny k-entry prefix stays serial.
-        __shared__ int64_t s_predcand[PMH_MAX_RUNS];
-        if (tid < k) {
-            int32_t a = c0[tid], b = c1[tid];
-            int32_t ext = (b < (int32_t)lens[tid]) ? 1 : 0;
-            sm.seglen[tid] = (b - a) + ext;
-            s_predcand[tid] =
-                a > 0 ? key_at(keys[tid].addr0, a - 1, keys[tid].esize)
-                      : INT64_MIN;
-            // reuse head[] as a tiny flag channel for "has predecessor"
-            sm.head[tid] = a > 0;
-        }
+    const int tid = threadIdx.x;
+    // the staged columns are contiguous: keep their bases in LDS, once
+    if (tid < k) {
+        sm.rb[tid].key = keys[tid].addr0;
+        sm.rb[tid].seq = seqs[tid].addr0;
+        sm.rb[tid].kind = kinds[tid].addr0;
+        sm.rb[tid].tomb = tombs ? tombs[tid] : 0;
+    }
+    const int kes = keys[0].esize;  // the key type is uniform across runs
+    __syncthreads();
+    // Staging is software-pipelined across this block's tiles: the loads of
+    // tile t + gridDim.x are issued into registers right after tile t's
+    // registers went to LDS, and land during tile t's merge and walk.
+    // The partial-update walk, and the tombstone bytes, leave no registers
+    // for a tile in flight (it would spill): there a tile's loads are
+    // issued, flat, at its own start, in two halves.
+    constexpr bool PIPE = !PU && !TOMBS;
+    constexpr int HALF = PMH_TILE_ITER / 2;
+    TileRegs<TOMBS> rg;
+    if (PIPE && (int64_t)blockIdx.x < n_tiles)
+        tile_prefetch<KM, TOMBS, 4>(sm, sm.setup[0], cuts, lens, blockIdx.x,
+                                    k, kes, tid, rg);
+    int cb = 0;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;
+         tile += gridDim.x, cb ^= 1) {
+        if (!PIPE)
+            tile_prefetch<KM, TOMBS, 2, 0, HALF>(sm, sm.setup[cb], cuts, lens,
+                                                 tile, k, kes, tid, rg);
+        // publishes setup[cb] and ends the previous tile's LDS reads
         __syncthreads();
-        if (tid == 0) {
-            int32_t off = 0;
-            int32_t real = 0;
-            int64_t pred = 0;
-            int hp = 0;
-            for (int r = 0; r < k; r++) {
-                sm.segoff[r] = off;
-                int32_t ext_len = sm.seglen[r];
-                int32_t real_len = c1[r] - c0[r];
-                real += real_len;
-                off += ext_len;
-                if (sm.head[r]) {
-                    if (!hp || s_predcand[r] > pred) pred = s_predcand[r];
-                    hp = 1;
+        const TileSetup &st = sm.setup[cb];
+        const int32_t M = st.mtotal;
+        const int32_t Mreal = st.mreal;
+
+        // --- registers -> LDS (flat slots), then prefetch the next tile
+        auto store_slots = [&](int s0, int ns) {
+#pragma unroll
+            for (int s = s0; s < s0 + ns; s++) {
+                const int32_t e = tid + s * PMH_TILE_THREADS;
+                if (e < M) {
+                    const int32_t kd = rg.kind[s];
+                    const bool dead = TOMBS && rg.tomb[TOMBS ? s : 0];
+                    if (PU && rrod && !seqg && kd == 1 && !dead && err_flag)
+                        atomicOr(err_flag, 1u);  // UPDATE_BEFORE: not in v1
+                                                 // RROD (sequence groups
+                                                 // accept it)
+                    sm.skey[e] =
+                        kes == 8 ? rg.key[s] : (int64_t)(int32_t)rg.key[s];
+                    sm.sseq[e] = dead ? PMH_DEAD
+                                      : (rg.seq[s] << 1) |
+                                            (int64_t)(kd == 0 || kd == 2);
+                    sm.perm[0][e] = (uint16_t)e;
                 }
             }
-            sm.segoff[k] = off;
-            sm.mtotal = off;
-            sm.mreal = real;
-            sm.predkey = pred;
-            sm.haspred = hp;
-            sm.nemit = 0;
+        };
+        if constexpr (PIPE) {
+            store_slots(0, PMH_TILE_ITER);
+        } else {
+            store_slots(0, HALF);
+            tile_prefetch<KM, TOMBS, 2, HALF, HALF>(sm, sm.setup[cb], cuts,
+                                                    lens, tile, k, kes, tid,
+                                                    rg);
+            store_slots(HALF, HALF);
         }
+        if (tid < 64) {
+            // predecessor key: max over the runs' candidates, which sit in
+            // the first k <= 32 lanes of wave 0
+            // (a run has one iff its cut, rowoff + segoff, is not 0)
+            int64_t pk = kes == 8 ? rg.pred : (int64_t)(int32_t)rg.pred;
+            const int pr = tid & (PMH_MAX_RUNS - 1);
+            int hp = tid < k && st.rowoff[pr] + st.segoff[pr] > 0;
+            for (int off = PMH_MAX_RUNS / 2; off > 0; off >>= 1) {
+                const int64_t opk = __shfl_xor(pk, off, 64);
+                const int ohp = __shfl_xor(hp, off, 64);
+                if (ohp && (!hp || opk > pk)) pk = opk;
+                hp |= ohp;
+            }
+            if (tid == 0) {
+                sm.predkey = pk;
+                sm.haspred = hp;
+            }
+        }
+        if (PIPE && tile + gridDim.x < n_tiles)
+            tile_prefetch<KM, TOMBS, 4>(sm, sm.setup[cb ^ 1], cuts, lens,
+                                        tile + gridDim.x, k, kes, tid, rg);
         __syncthreads();
-        const int32_t M = sm.mtotal;
-        const int32_t Mreal = sm.mreal;
         if (Mreal == 0) {
             if (tid == 0) {
                 tile_counts[tile] = 0;
                 if (cl_counts) cl_counts[tile] = 0;
             }
-            __syncthreads();
             continue;
         }
-
-        // --- stage key/seq/kind segments into LDS (coalesced per run).
-        // Column base addresses hoisted out of the element loop: the staged
-        // columns are contiguous, and re-reading the DevCol descriptor per
-        // element serialized the loads (ablation: staging was 1.5 of 3.6 ms).
-        for (int r = 0; r < k; r++) {
-            int32_t off = sm.segoff[r], len = sm.seglen[r];
-            int64_t base = c0[r];
-            const int kes = keys[r].esize;
-            const uint64_t kaddr0 = keys[r].addr0 + (uint64_t)base * kes;
-            const int64_t *saddr =
-                reinterpret_cast<const int64_t *>(seqs[r].addr0) + base;
-            const int32_t *daddr =
-                reinterpret_cast<const int32_t *>(kinds[r].addr0) + base;
-            const uint8_t *tb =
-                tombs && tombs[r]
-                    ? reinterpret_cast<const uint8_t *>(tombs[r]) + base
-                    : nullptr;
-            for (int32_t i = tid; i < len; i += blockDim.x) {
-                sm.skey[off + i] = key_at(kaddr0, i, kes);
-                int32_t kd = daddr[i];
-                const bool dead = tb && tb[i];
-                if (PU && rrod && !seqg && kd == 1 && !dead && err_flag)
-                    atomicOr(err_flag, 1u);  // UPDATE_BEFORE: not in v1 RROD
-                                             // (sequence groups accept it)
-                sm.sseq[off + i] =
-                    dead ? PMH_DEAD
-                         : (saddr[i] << 1) | (int64_t)(kd == 0 || kd == 2);
-                sm.perm[0][off + i] = (uint16_t)(off + i);
-            }
-        }
-        __syncthreads();
         if (ablate == 1) {
             // keep staged data live; counts stay in {0,1} so the downstream
             // scan/emit of an ablated (profiling-only) run never goes OOB
@@ -536,7 +712,6 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 int64_t x = sm.skey[M - 1] ^ sm.sseq[M - 1];
                 tile_counts[tile] = (int32_t)((x ^ (x >> 32)) & 1);
             }
-            __syncthreads();
             continue;
         }
 
@@ -558,14 +733,14 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 while (remaining > 0) {
                     // pair p covers output ranks [segoff[a0], segoff[b1])
                     while ((p + 1) * 2 * width < k &&
-                           sm.segoff[(p + 1) * 2 * width] <= o)
+                           st.segoff[(p + 1) * 2 * width] <= o)
                         p++;
                     int a0 = p * 2 * width;
                     int amid = a0 + width < k ? a0 + width : k;
                     int b1 = a0 + 2 * width < k ? a0 + 2 * width : k;
-                    int32_t abase = sm.segoff[a0];
-                    int32_t la = sm.segoff[amid] - abase;
-                    int32_t lb = sm.segoff[b1] - sm.segoff[amid];
+                    int32_t abase = st.segoff[a0];
+                    int32_t la = st.segoff[amid] - abase;
+                    int32_t lb = st.segoff[b1] - st.segoff[amid];
                     int64_t d = o - abase;  // rank within pair
                     int32_t lim = la + lb - (int32_t)d;
                     if (lim <= 0) break;  // past the last pair
@@ -593,20 +768,43 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
         if (ablate == 2) {
             if (tid == 0)
                 tile_counts[tile] = ((int32_t)mo[M - 1] ^ (int32_t)mo[0]) & 1;
-            __syncthreads();
             continue;
         }
 
         // --- group heads + previous-tile continuation skip
+        const int64_t predkey = sm.predkey;
+        const bool haspred = sm.haspred;
         for (int32_t i = tid; i < M; i += blockDim.x) {
             int64_t kk = sm.skey[mo[i]];
             uint8_t h = (i == 0) ? 1 : (kk != sm.skey[mo[i - 1]]);
             // records continuing the previous tile's last group are not
             // heads here (that tile consumed them as its extras)
-            if (sm.haspred && kk == sm.predkey) h = 0;
+            if (haspred && kk == predkey) h = 0;
             sm.head[i] = h;
         }
         __syncthreads();
+        // segment element -> run, branch-free (segoff entries past k hold
+        // M > sx). Up to 8 runs: the block-uniform offsets are read once per
+        // tile into scalar registers and an element's run is a count of
+        // compares; beyond, a log2(KM)-step search in LDS.
+        int32_t sseg[KM <= 8 ? KM : 1];
+        if constexpr (KM <= 8) {
+#pragma unroll
+            for (int j = 1; j < KM; j++)
+                sseg[j] = __builtin_amdgcn_readfirstlane(st.segoff[j]);
+        }
+        auto run_of = [&](int32_t sx) -> int {
+            int r = 0;
+            if constexpr (KM <= 8) {
+#pragma unroll
+                for (int j = 1; j < KM; j++) r += sseg[j] <= sx ? 1 : 0;
+            } else {
+#pragma unroll
+                for (int step = KM / 2; step > 0; step >>= 1)
+                    r += st.segoff[r + step] <= sx ? step : 0;
+            }
+            return r;
+        };
 
         // block-wide exclusive scan (wave shuffle scans + one barrier):
         // the former Hillis-Steele block scans cost 16 __syncthreads per
@@ -697,12 +895,9 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                             if (!rrod && !seqg && !aggr && gn > 1 &&
                                 !ps2m_isadd(sm.sseq[s]))
                                 bad_kind = true;
-                            int r = 0;
-                            while (r + 1 <= k - 1 &&
-                                   sm.segoff[r + 1] <= (int32_t)s)
-                                r++;
-                            uint32_t grow = (uint32_t)(
-                                c0[r] + ((int32_t)s - sm.segoff[r]));
+                            const int r = run_of(s);
+                            uint32_t grow =
+                                (uint32_t)((int32_t)s + st.rowoff[r]);
                             mout[m_off + nm + x] = ((uint32_t)r << PMH_ROW_BITS) | grow;
                         }
                     }
@@ -746,22 +941,21 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 tile_counts[tile] = total_g;
                 gout[total_g] = (uint16_t)total_m;  // sentinel
             }
-            __syncthreads();
             continue;
         }
 
         if (ablate == 3) {
             if (tid == 0)
                 tile_counts[tile] = ((int32_t)mo[0] ^ (int32_t)sm.head[0]) & 1;
-            __syncthreads();
             continue;
         }
         // --- emit winners of owned groups, in key order.
         // A group is owned iff its head is a real (rank < Mreal) head; the
         // winner — DeduplicateMergeFunction's surviving record — is found
         // inline while walking the group's <= k members (max by packed
-        // (eligible, seq, isAdd)). Two passes per thread over a contiguous
-        // head range (count, then write at the scanned offset).
+        // (eligible, seq, isAdd)). Each thread walks a contiguous head range
+        // and writes at the scanned offset; only the changelog producers
+        // walk twice (count, then write).
         const int32_t per = (Mreal + (int32_t)blockDim.x - 1) / blockDim.x;
         int32_t my_lo = tid * per;
         int32_t my_hi = my_lo + per < Mreal ? my_lo + per : Mreal;
@@ -777,15 +971,28 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             cl ? &cl_entries[tile * 2 * (tile_rows + PMH_MAX_RUNS)] : nullptr;
         // map seg index -> packed (run, global row)
         auto packm = [&](uint16_t sx) -> uint64_t {
-            int r = 0;
-            while (r + 1 <= k - 1 && sm.segoff[r + 1] <= (int32_t)sx) r++;
+            const int r = run_of(sx);
             return ((uint32_t)r << PMH_ROW_BITS) |
-                   (uint32_t)(c0[r] + ((int32_t)sx - sm.segoff[r]));
+                   (uint32_t)((int32_t)sx + st.rowoff[r]);
         };
+        // Without changelog entries the walk runs once: the count pass parks
+        // each kept winner at its head's rank in skey[] (dead after the head
+        // pass; a thread reads back only its own <= PMH_TILE_ITER ranks) and
+        // `kept` marks them; after the scan they are just stored.
+        const bool one_walk = !LK && !cl;
+        uint32_t *wpark = reinterpret_cast<uint32_t *>(sm.skey);
+        uint32_t kept = 0;
         int32_t total = 0;
         int32_t my_off = 0;
         int32_t my_cl = 0;
         for (int pass = 0; pass < 2; pass++) {
+            if (pass == 1 && one_walk) {
+                int32_t n = 0;
+                for (int32_t j = 0; j < my_hi - my_lo; j++)
+                    if ((kept >> j) & 1)
+                        wout[my_off + n++] = wpark[my_lo + j];
+                break;
+            }
             int32_t nloc = 0, ncl = 0;
             for (int32_t i = my_lo; i < my_hi; i++) {
                 if (!sm.head[i]) continue;
@@ -804,11 +1011,7 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                         const uint16_t sx = mo[x];
                         const int64_t v = sm.sseq[sx];
                         if (v != PMH_DEAD) {
-                            int r = 0;
-                            while (r + 1 <= k - 1 &&
-                                   sm.segoff[r + 1] <= (int32_t)sx)
-                                r++;
-                            const int lv = run_levels[r];
+                            const int lv = run_levels[run_of(sx)];
                             if (lv > 0) {
                                 // pickHighLevel: lowest level; a level tie
                                 // goes to the earlier record in merge order
@@ -927,11 +1130,7 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                             e_best = e;
                         }
                         if (cl) {
-                            int r = 0;
-                            while (r + 1 <= k - 1 &&
-                                   sm.segoff[r + 1] <= (int32_t)mo[x])
-                                r++;
-                            if (run_levels[r] == max_level) {
+                            if (run_levels[run_of(mo[x])] == max_level) {
                                 s_top = mo[x];
                                 n_top++;
                             }
@@ -984,8 +1183,12 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     atomicOr(err_flag, 2u);  // FirstRow rejects retracts
                 if (!e_best && nlive > 1) continue;  // all records ignored
                 if (drop_delete && !(v_best & 1)) continue;
-                if (pass == 1)
+                if (one_walk) {
+                    wpark[i] = (uint32_t)packm(s_best);
+                    kept |= 1u << (i - my_lo);
+                } else if (pass == 1) {
                     wout[my_off + nloc] = (uint32_t)packm(s_best);
+                }
                 nloc++;
             }
             if (pass == 0) {
@@ -1020,7 +1223,6 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             }
         }
         if (tid == 0) tile_counts[tile] = total;
-        __syncthreads();
     }
 }
 
@@ -1872,25 +2074,40 @@ __global__ void k_emit_dense(const DevCol *cols, const uint8_t *col_dtype,
 // Exclusive scan of tile_counts (single workgroup, chunked).
 __global__ void k_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
                              int64_t *tile_offsets, int64_t *total_out) {
-    __shared__ int64_t s[PMH_TILE_THREADS];
-    __shared__ int64_t running;
-    if (threadIdx.x == 0) running = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_tiles; base += blockDim.x) {
-        int64_t i = base + threadIdx.x;
-        int64_t v = i < n_tiles ? tile_counts[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < (int)blockDim.x; d <<= 1) {
-            int64_t add = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
+    // wave shuffle scan + one barrier per chunk (k_merge_tiles' block scan);
+    // the wave totals alternate between two buffers, so the next chunk's
+    // barrier also orders this chunk's reads before the buffer's reuse
+    constexpr int NW = PMH_TILE_THREADS / 64;
+    __shared__ int64_t wave_tot[2][NW];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    int64_t running = 0;  // every thread carries the same value
+    int buf = 0;
+    int64_t i = threadIdx.x;
+    int64_t v = i < n_tiles ? tile_counts[i] : 0;
+    for (int64_t base = 0; base < n_tiles; base += PMH_TILE_THREADS) {
+        // next chunk's load in flight across the scan
+        const int64_t in = i + PMH_TILE_THREADS;
+        const int64_t vn = in < n_tiles ? tile_counts[in] : 0;
+        int64_t incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            int64_t up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
         }
-        if (i < n_tiles) tile_offsets[i] = running + s[threadIdx.x] - v;
+        if (lane == 63) wave_tot[buf][wv] = incl;
         __syncthreads();
-        if (threadIdx.x == 0) running += s[blockDim.x - 1];
-        __syncthreads();
+        int64_t add = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const int64_t t = wave_tot[buf][w];
+            if (w < wv) add += t;
+            tot += t;
+        }
+        if (i < n_tiles) tile_offsets[i] = running + add + incl - v;
+        running += tot;
+        buf ^= 1;
+        i = in;
+        v = vn;
     }
     if (threadIdx.x == 0) *total_out = running;
 }
@@ -4277,7 +4494,19 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
                                   const uint32_t *probe_words,
                                   const int64_t *probe_off,
                                   hipStream_t stream) {
-    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
+    // A block pipelines its staging across its tiles, but fewer, longer-lived
+    // blocks did not pay: 512 / 1024 / 2048 / 4096 blocks measured 1.47 /
+    // 1.47 / 1.45 / 1.44 ms at 8 x 10M rows and 7.33 / 7.34 / 7.29 / 7.05 ms
+    // at 16 x 20M (profiles/merge_phases.md), so the grid stays at 4096.
+    // PMH_MERGE_BLOCKS overrides it (read per launch: tests vary it within
+    // a process).
+    constexpr int64_t PMH_MERGE_BLOCKS_DEFAULT = 4096;
+    int64_t max_blocks = PMH_MERGE_BLOCKS_DEFAULT;
+    if (const char *e = getenv("PMH_MERGE_BLOCKS")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= 65535) max_blocks = v;
+    }
+    int blocks = n_tiles < max_blocks ? (int)n_tiles : (int)max_blocks;
     const bool pu = flags & 4, fr = flags & 8,
                lk = flags & PMH_FLAG_LOOKUP;
     auto launch = [&](auto kern) {
@@ -4287,14 +4516,35 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
                            group_start, err_flag, run_levels, max_level,
                            cl_entries, cl_counts, probe_words, probe_off);
     };
-    if (lk)
-        launch(k_merge_tiles<false, false, true>);  // deduplicate only
-    else if (pu)
-        launch(k_merge_tiles<true, false>);  // PU/agg never first-row
-    else if (fr)
-        launch(k_merge_tiles<false, true>);
+    // KM = unrolled run bound of the staging setup (k_partition_wave's)
+    // and TOMBS = deletion-vector bytes ride along (their registers stay out
+    // of the plain kernels)
+    auto launch_km = [&](auto km, auto tb) {
+        constexpr int KM = decltype(km)::value;
+        constexpr bool TB = decltype(tb)::value;
+        if (lk)
+            launch(k_merge_tiles<false, false, true, KM, TB>);  // dedup only
+        else if (pu)
+            launch(k_merge_tiles<true, false, false, KM, TB>);  // never FR
+        else if (fr)
+            launch(k_merge_tiles<false, true, false, KM, TB>);
+        else
+            launch(k_merge_tiles<false, false, false, KM, TB>);
+    };
+    auto launch_k = [&](auto tb) {
+        if (k <= 4)
+            launch_km(std::integral_constant<int, 4>{}, tb);
+        else if (k <= 8)
+            launch_km(std::integral_constant<int, 8>{}, tb);
+        else if (k <= 16)
+            launch_km(std::integral_constant<int, 16>{}, tb);
+        else
+            launch_km(std::integral_constant<int, PMH_MAX_RUNS>{}, tb);
+    };
+    if (tombs)
+        launch_k(std::true_type{});
     else
-        launch(k_merge_tiles<false, false>);
+        launch_k(std::false_type{});
     return hipGetLastError();
 }
 
