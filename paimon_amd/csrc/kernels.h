@@ -303,8 +303,14 @@ hipError_t pmh_launch_emit_dense(const DevCol *cols,
                                  uint8_t *const *out_valid,
                                  hipStream_t stream);
 
+// Winner gather. n_desc = run slots of `cols` that a winner word can name
+// (the k merge runs plus a lookup plan's level slots); contiguous = every one
+// of those n_desc * n_cols descriptors has n_pages == 1. Contiguous plans
+// whose descriptor table fits LDS run k_emit_contig; the rest, and
+// PMH_EMIT_LEGACY=1, run the paged k_emit.
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
                            const uint8_t *col_nullable, int n_cols, int k,
+                           int n_desc, int contiguous,
                            const uint32_t *winners,
                            const int32_t *tile_counts,
                            const int64_t *tile_offsets, int64_t n_tiles,

@@ -2119,11 +2119,13 @@ __global__ void k_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
 template <int R>
 __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
                        const uint8_t *col_dtype, const uint8_t *col_nullable,
-                       int n_cols, int k, const uint32_t *winners,
+                       int n_cols, int n_emit, int k, const uint32_t *winners,
                        const int32_t *tile_counts,
                        const int64_t *tile_offsets, int64_t n_tiles,
                        int64_t tile_rows, const int64_t *total_out,
                        void *const *out_ptrs, uint8_t *const *out_valid) {
+    // n_emit == n_cols except under the profiling-only PMH_EMIT_COLS knob
+    // (the columns past it are then left unwritten).
     // Flat grid-stride over the DENSE output index space (tile_offsets is an
     // exclusive scan of tile_counts, so tile t owns output ranks
     // [off[t], off[t]+cnt[t]) contiguously). R rows per thread iteration:
@@ -2181,7 +2183,7 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
                 row[x] = row[0];
             }
         }
-        for (int c = 0; c < n_cols; c++) {
+        for (int c = 0; c < n_emit; c++) {
             if (col_nullable[c] && out_valid[c]) {
                 // winner's validity byte (dedup keeps the record as-is)
 #pragma unroll
@@ -2241,6 +2243,292 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
             default: break;
             }
         }
+    }
+}
+
+// ------------------------------------------------------ k_emit_contig
+//
+// k_emit for plans whose columns are all contiguous (n_pages == 1 in every
+// descriptor, which is every plan built today). Same work division: a
+// contiguous output slice per block, wave-strided rows, dead lanes repeat
+// row 0's gather with their stores guarded. What differs is that nothing
+// inside the row / column loops depends on a descriptor read from global
+// memory -- k_emit paid three dependent round trips per row and column
+// (n_pages, addr0, data), with every wait a full drain, so its R "parallel"
+// gathers ran one after another (profiles/emit_phases.md):
+//  * addr0 / valid0 of the n_desc runs the winners can name, and per column
+//    {list position, output pointer, validity output pointer}, are staged in
+//    LDS once per block; a gather address is one LDS read + row * width;
+//  * the tile that owns slice_lo is searched once per block and EMIT_WIN + 1
+//    tile offsets from there are staged; each thread's tile cursor walks that
+//    window in registers/LDS (global reads only past the window, which takes
+//    a run of empty tiles or a very coarse grid);
+//  * the R winner loads of an iteration are issued together;
+//  * columns are ordered into four lists by OUTPUT width (1 / 2 / 4 / 8
+//    bytes; the first three load 4-byte stored values) and each list is
+//    walked in groups of G: all G x R gathers are issued, then the G x R
+//    stores, each waiting on its own gather only;
+//  * data moves through address_space(1) pointers (global_*, not flat_*).
+// Barriers: three, all in the prologue, reached by every thread of a block
+// that has a non-empty slice; a block with an empty slice leaves before the
+// first one (block-uniform). The per-thread exit sits after the last barrier.
+constexpr int EMIT_WIN = 64;
+constexpr int EMIT_THREADS = 256;
+constexpr int EMIT_LDS_MAX = 16384;  // LDS never the occupancy limit
+
+// LDS bytes of k_emit_contig's tables (the launcher falls back to k_emit
+// when they exceed EMIT_LDS_MAX)
+static inline int64_t emit_contig_lds(int64_t n_desc, int64_t n_cols) {
+    return 16 * n_desc * n_cols + 16 * n_cols + 8 * (EMIT_WIN + 1) + 16 +
+           2 * n_cols;
+}
+
+template <typename T>
+DEV void gstore(uint64_t addr, T v) {
+    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
+}
+
+DEV uint64_t uniform64(uint64_t v) {  // block-uniform value -> SGPR pair
+    // the builtin returns int: widen each half as unsigned, or a low half
+    // with bit 31 set would sign-extend over the high half
+    const uint32_t hi =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    const uint32_t lo =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    return ((uint64_t)hi << 32) | (uint64_t)lo;
+}
+
+// Store row x of this thread's R rows at output index base + x *
+// EMIT_THREADS + tid. ob = column base + base * sizeof(T) is block-uniform
+// (a scalar register pair), so the store addresses as scalar base + one
+// small per-lane offset shared by all x + an immediate.
+template <typename T>
+DEV void emit_store(uint64_t ob, int x, uint32_t tid, T v) {
+    gstore<T>(ob + (uint64_t)(tid * (uint32_t)sizeof(T)) +
+                  (uint64_t)(x * EMIT_THREADS * (int)sizeof(T)),
+              v);
+}
+
+// G columns at list positions [p, p + G) for this thread's R rows: all G x R
+// gathers are issued, then the G x R stores. L is the stored (loaded) type, S
+// the output type the store narrows to. s_addr / s_valid are indexed
+// [run * n_cols + position]; dl[x] is row x's run * n_cols. FULL: every lane
+// of the block has all R rows live (block-uniform), so no store is guarded.
+// With FULL every loaded register is consumed on every path; that and the
+// absence of any dtype branch between loads and stores is what lets the
+// compiler issue the next group's gathers without first draining this
+// group's stores.
+template <typename L, typename S, int G, int R, bool FULL>
+DEV void emit_group(const uint64_t *s_addr, const uint64_t *s_valid,
+                    const uint64_t *s_out, const uint64_t *s_ov, int p,
+                    const int (&dl)[R], const uint32_t (&row)[R],
+                    int64_t base, uint32_t tid, int nr) {
+    // validity bytes of the group's nullable columns (valid0 == 0: the run
+    // staged no nulls for this column)
+#pragma nounroll
+    for (int g = 0; g < G; g++) {
+        const uint64_t ov0 = uniform64(s_ov[p + g]);
+        if (!ov0) continue;
+        const uint64_t ov = ov0 + (uint64_t)base;
+        uint8_t vb[R];
+#pragma unroll
+        for (int x = 0; x < R; x++) {
+            const uint64_t va = s_valid[dl[x] + p + g];
+            vb[x] = va ? gload<uint8_t>(va + row[x]) : (uint8_t)1;
+        }
+#pragma unroll
+        for (int x = 0; x < R; x++)
+            if (FULL || x < nr) emit_store<uint8_t>(ov, x, tid, vb[x]);
+    }
+    L v[G][R];
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int x = 0; x < R; x++)
+            v[g][x] = gload<L>(
+                s_addr[dl[x] + p + g] +
+                (uint64_t)(row[x] * (uint32_t)sizeof(L)));  // row < 2^27
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const uint64_t ob =
+            uniform64(s_out[p + g] + (uint64_t)base * sizeof(S));
+#pragma unroll
+        for (int x = 0; x < R; x++)
+            if (FULL || x < nr) emit_store<S>(ob, x, tid, (S)v[g][x]);
+    }
+}
+
+// One list of columns, positions [p_lo, p_hi): groups of G, then the
+// remainder in groups of G / 2 ... 1.
+template <typename L, typename S, int G, int R, bool FULL>
+DEV void emit_list(const uint64_t *s_addr, const uint64_t *s_valid,
+                   const uint64_t *s_out, const uint64_t *s_ov, int p_lo,
+                   int p_hi, const int (&dl)[R], const uint32_t (&row)[R],
+                   int64_t base, uint32_t tid, int nr) {
+    int p = p_lo;
+    for (; p + G <= p_hi; p += G)
+        emit_group<L, S, G, R, FULL>(s_addr, s_valid, s_out, s_ov, p, dl, row,
+                                     base, tid, nr);
+    if constexpr (G > 1)
+        emit_list<L, S, G / 2, R, FULL>(s_addr, s_valid, s_out, s_ov, p, p_hi,
+                                        dl, row, base, tid, nr);
+}
+
+template <int R, int G4, int G8>
+__launch_bounds__(EMIT_THREADS) __global__
+void k_emit_contig(const DevCol *cols /* n_desc * n_cols, run-major */,
+                   const uint8_t *col_dtype, const uint8_t *col_nullable,
+                   int n_cols, int n_emit, int n_desc,
+                   const uint32_t *winners, const int64_t *tile_offsets,
+                   int64_t n_tiles, int64_t tile_rows,
+                   const int64_t *total_out, void *const *out_ptrs,
+                   uint8_t *const *out_valid) {
+    extern __shared__ uint64_t emit_smem[];
+    const int n_ent = n_desc * n_cols;
+    uint64_t *s_addr = emit_smem;                  // [n_ent] run, position
+    uint64_t *s_valid = s_addr + n_ent;            // [n_ent] run, position
+    uint64_t *s_out = s_valid + n_ent;             // [n_cols] by position
+    uint64_t *s_ov = s_out + n_cols;               // [n_cols] by position
+    int64_t *s_toff = (int64_t *)(s_ov + n_cols);  // [EMIT_WIN + 1]
+    int *s_cnt = (int *)(s_toff + EMIT_WIN + 1);   // list lengths {1,2,4,8}
+    uint8_t *s_pos = (uint8_t *)(s_cnt + 4);       // [n_cols] column -> position
+    uint8_t *s_cls = s_pos + n_cols;               // [n_cols] by column
+
+    const int tid = threadIdx.x;
+    const int64_t total = *total_out;
+    const int64_t per_block =
+        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
+    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
+    const int64_t slice_hi = slice_lo + per_block < total
+                                 ? slice_lo + per_block : total;
+    if (slice_lo >= slice_hi) return;  // block-uniform, before any barrier
+
+    // a column's list = the width its output is stored at, by dtype as in
+    // k_emit's switch (1 / 2 narrow INT32-stored TINYINT / SMALLINT; 5 / 6 /
+    // 7 move as raw 32 / 64 / 32-bit words); 0 = not emitted
+    auto dt_class = [](int dt) {
+        return dt == 1 ? 1
+               : dt == 2 ? 2
+               : (dt == 3 || dt == 5 || dt == 7) ? 4
+               : (dt == 4 || dt == 6) ? 8
+                                      : 0;
+    };
+    for (int c = tid; c < n_cols; c += EMIT_THREADS)
+        s_cls[c] = c < n_emit ? dt_class(col_dtype[c]) : 0;
+    // the tile that owns slice_lo (block-uniform search, every thread)
+    int64_t t0;
+    {
+        int64_t lo = 0, hi = n_tiles - 1;
+        while (lo < hi) {
+            int64_t mid = (lo + hi + 1) >> 1;
+            if (tile_offsets[mid] <= slice_lo) lo = mid;
+            else hi = mid - 1;
+        }
+        t0 = lo;
+    }
+    for (int j = tid; j <= EMIT_WIN; j += EMIT_THREADS)
+        s_toff[j] = t0 + j < n_tiles ? tile_offsets[t0 + j] : INT64_MAX;
+    __syncthreads();
+    // order the columns: the 1-, 2-, 4- and 8-byte lists one after another,
+    // each in column order
+    for (int c = tid; c < n_cols; c += EMIT_THREADS) {
+        const int cls = s_cls[c];
+        int n_of[4] = {0, 0, 0, 0};  // list lengths, by log2(width)
+        int before = 0;
+        for (int j = 0; j < n_cols; j++) {
+            const int cj = s_cls[j];
+#pragma unroll
+            for (int w = 0; w < 4; w++) n_of[w] += cj == (1 << w);
+            before += (j < c && cj == cls);
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) s_cnt[w] = n_of[w];
+        }
+        if (cls) {
+            int p = before;
+#pragma unroll
+            for (int w = 0; w < 3; w++) p += (1 << w) < cls ? n_of[w] : 0;
+            s_pos[c] = (uint8_t)p;
+            s_out[p] = (uint64_t)out_ptrs[c];
+            s_ov[p] = col_nullable[c] ? (uint64_t)out_valid[c] : 0;
+        }
+    }
+    __syncthreads();
+    // descriptors of the emitted columns, read once
+    for (int e = tid; e < n_ent; e += EMIT_THREADS) {
+        const int r = e / n_cols, c = e - r * n_cols;
+        if (!s_cls[c]) continue;
+        const int d = r * n_cols + s_pos[c];
+        s_addr[d] = cols[e].addr0;
+        s_valid[d] = cols[e].valid0;
+    }
+    __syncthreads();
+    const int e1 = s_cnt[0], e2 = e1 + s_cnt[1], e4 = e2 + s_cnt[2],
+              e8 = e4 + s_cnt[3];  // list ends
+
+    // tile cursor: tile t0 + tr owns ranks [cur, nxt); offsets come from the
+    // window, and from global memory only past it
+    const int64_t wstride = tile_rows + PMH_MAX_RUNS;
+    auto toff = [&](int64_t j) -> int64_t {
+        if (j >= n_tiles) return INT64_MAX;
+        return j - t0 <= EMIT_WIN
+                   ? s_toff[j - t0]
+                   : gload<int64_t>((uint64_t)(tile_offsets + j));
+    };
+    int tr = 0;
+    int64_t cur = s_toff[0];
+    int64_t nxt = s_toff[1];
+    for (int64_t base = slice_lo; base < slice_hi;
+         base += (int64_t)EMIT_THREADS * R) {
+        const int64_t i0 = base + tid;
+        if (i0 >= slice_hi) break;  // after the last barrier
+        uint64_t wa[R];
+        int nr = 0;
+#pragma unroll
+        for (int x = 0; x < R; x++) {
+            const int64_t i = i0 + x * EMIT_THREADS;
+            if (i < slice_hi) {
+                nr = x + 1;
+                // dense ranks: advance while i falls past the tile's count
+                // (nxt is INT64_MAX past the last tile)
+                while (nxt <= i) {
+                    tr++;
+                    cur = nxt;
+                    nxt = toff(t0 + tr + 1);
+                }
+                wa[x] = (uint64_t)(winners + (t0 + tr) * wstride + (i - cur));
+            } else {  // dead lane: repeat x = 0's gather, stores are guarded
+                wa[x] = wa[0];
+            }
+        }
+        uint32_t packed[R];
+#pragma unroll
+        for (int x = 0; x < R; x++) packed[x] = gload<uint32_t>(wa[x]);
+        int dl[R];
+        uint32_t row[R];
+#pragma unroll
+        for (int x = 0; x < R; x++) {
+            dl[x] = (int)(packed[x] >> PMH_ROW_BITS) * n_cols;
+            row[x] = packed[x] & PMH_ROW_MASK;
+        }
+        auto lists = [&](auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            const uint32_t utid = (uint32_t)tid;
+            emit_list<int32_t, int8_t, G4, R, FULL>(
+                s_addr, s_valid, s_out, s_ov, 0, e1, dl, row, base, utid, nr);
+            emit_list<int32_t, int16_t, G4, R, FULL>(
+                s_addr, s_valid, s_out, s_ov, e1, e2, dl, row, base, utid, nr);
+            emit_list<int32_t, int32_t, G4, R, FULL>(
+                s_addr, s_valid, s_out, s_ov, e2, e4, dl, row, base, utid, nr);
+            emit_list<int64_t, int64_t, G8, R, FULL>(
+                s_addr, s_valid, s_out, s_ov, e4, e8, dl, row, base, utid, nr);
+        };
+        // block-uniform: only a slice's last iteration has dead rows
+        if (base + (int64_t)EMIT_THREADS * R <= slice_hi)
+            lists(std::true_type{});
+        else
+            lists(std::false_type{});
     }
 }
 
@@ -4423,15 +4711,11 @@ void k_zstd_pages(const uint8_t *src, const ZstdJob *jobs, int n,
 
 // emit-family x-block count: 4096 measured ~5% faster than 2048 at C2
 // (smaller contiguous output slices balance the tail); PMH_EMIT_BLOCKS
-// is the A/B override.
+// is the A/B override (read per launch: tests vary it within a process).
 static int emit_grid() {
-    static int xblocks = 0;
-    if (xblocks <= 0) {
-        const char *b = getenv("PMH_EMIT_BLOCKS");
-        xblocks = b ? atoi(b) : 0;
-        if (xblocks <= 0) xblocks = 4096;
-    }
-    return xblocks;
+    const char *b = getenv("PMH_EMIT_BLOCKS");
+    const int xblocks = b ? atoi(b) : 0;
+    return xblocks > 0 && xblocks <= 65535 ? xblocks : 4096;
 }
 
 // ---------------------------------------------------------------- launchers
@@ -4706,25 +4990,61 @@ hipError_t pmh_launch_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
 
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
                            const uint8_t *col_nullable, int n_cols, int k,
+                           int n_desc, int contiguous,
                            const uint32_t *winners,
                            const int32_t *tile_counts,
                            const int64_t *tile_offsets, int64_t n_tiles,
                            int64_t tile_rows, const int64_t *total_out,
                            void *const *out_ptrs, uint8_t *const *out_valid,
                            hipStream_t stream) {
-    // R = rows per thread iteration (independent gathers in flight);
-    // PMH_EMIT_R sweeps 4/6/8 (4 = measured default)
-    static int r_rows = 0;
-    if (r_rows <= 0) {
-        const char *e = getenv("PMH_EMIT_R");
-        r_rows = e ? atoi(e) : 4;
-        if (r_rows != 6 && r_rows != 8) r_rows = 4;
+    // Every knob is read per launch (tests vary them within a process).
+    // R = rows per thread iteration, G = 4-byte columns per gather group
+    // (8-byte columns go G / 2 at a time). PMH_EMIT_R sweeps 2/4 (legacy
+    // kernel: 4/6/8) and PMH_EMIT_G 2/4/8 (16 with R = 4). The defaults,
+    // R = 4 and G = 8, are the measured best although 126 VGPRs halve the
+    // occupancy: 32 gathers in flight per wave beat 8 waves per SIMD
+    // (DESIGN.md §7).
+    auto env_int = [](const char *name, int dflt) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : dflt;
+    };
+    const int r_rows = env_int("PMH_EMIT_R", 4);
+    const int g_cols = env_int("PMH_EMIT_G", 8);
+    // profiling-only: emit just the first PMH_EMIT_COLS columns (the rest of
+    // the output is then garbage; only emit_ms means anything under it)
+    int n_emit = env_int("PMH_EMIT_COLS", n_cols);
+    if (n_emit < 0 || n_emit > n_cols) n_emit = n_cols;
+    const int grid = emit_grid();
+    const int64_t lds = emit_contig_lds(n_desc, n_cols);
+    // k_emit_contig serves all-contiguous plans whose tables fit; position ->
+    // column bytes cap n_cols at 256
+    const bool contig = contiguous && n_desc >= 1 && n_cols <= 256 &&
+                        lds <= EMIT_LDS_MAX &&
+                        env_int("PMH_EMIT_LEGACY", 0) == 0;
+    if (contig) {
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(EMIT_THREADS), (size_t)lds,
+                               stream, cols, col_dtype, col_nullable, n_cols,
+                               n_emit, n_desc, winners, tile_offsets, n_tiles,
+                               tile_rows, total_out, out_ptrs, out_valid);
+        };
+        if (r_rows == 2) {
+            if (g_cols == 2) launch(k_emit_contig<2, 2, 1>);
+            else if (g_cols == 4) launch(k_emit_contig<2, 4, 2>);
+            else launch(k_emit_contig<2, 8, 4>);
+        } else {
+            if (g_cols == 2) launch(k_emit_contig<4, 2, 1>);
+            else if (g_cols == 4) launch(k_emit_contig<4, 4, 2>);
+            else if (g_cols == 16) launch(k_emit_contig<4, 16, 8>);
+            else launch(k_emit_contig<4, 8, 4>);
+        }
+        return hipGetLastError();
     }
     auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(emit_grid()), dim3(256), 0, stream,
-                           cols, col_dtype, col_nullable, n_cols, k, winners,
-                           tile_counts, tile_offsets, n_tiles, tile_rows,
-                           total_out, out_ptrs, out_valid);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, cols,
+                           col_dtype, col_nullable, n_cols, n_emit, k,
+                           winners, tile_counts, tile_offsets, n_tiles,
+                           tile_rows, total_out, out_ptrs, out_valid);
     };
     if (r_rows == 6)
         launch(k_emit<6>);

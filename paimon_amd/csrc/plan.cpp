@@ -609,6 +609,9 @@ struct Section {
     DevCol *seq_cols = nullptr;   // [k]
     DevCol *kind_cols = nullptr;  // [k]
     DevCol *all_cols = nullptr;   // [k * n_cols] run-major
+    // every descriptor built for this section (real runs + lookup slots) has
+    // n_pages == 1: the emit gather may address columns directly
+    bool cols_contig = true;
     int64_t *lens_dev = nullptr;
     int32_t *cuts = nullptr;
     uint32_t *winners = nullptr;
@@ -3576,6 +3579,7 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
                       run.cols[c].pages_dev, run.cols[c].n_pages,
                       plan->cols[c].stored_esize};
             allv[r * n_cols + c] = dc;
+            sec.cols_contig &= dc.n_pages == 1;
             if (c == 0) keyv[r] = dc;  // single-column key: the column itself
             if (c == seq_idx) seqv[r] = dc;
             if (c == kind_idx) kindv[r] = dc;
@@ -4824,7 +4828,8 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
             if (hb != hipSuccess) return fail("hier scan", hb);
             hb = pmh_launch_emit(sec.rall + (size_t)lo * n_cols,
                                  p->hier_dtype_dev, p->col_nullable_dev,
-                                 n_cols, kb, sec.winners, sec.tile_counts,
+                                 n_cols, kb, kb, sec.cols_contig,
+                                 sec.winners, sec.tile_counts,
                                  sec.tile_offsets, btiles, PMH_TILE_ROWS,
                                  sec.lens_dev + b, sec.bout_ptrs[b],
                                  sec.bout_valid[b], st);
@@ -4983,8 +4988,12 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
             sec.total_dev, sec.row_masks_dev, p->out_ptrs_dev,
             p->out_valid_dev, st);
     } else {
+        // a lookup winner may name a lookup-level slot past the k merge
+        // runs; a hierarchical chain reads its (contiguous) virtual runs
         e = pmh_launch_emit(sec.all_cols, p->col_dtype_dev,
-                            p->col_nullable_dev, n_cols, k, sec.winners,
+                            p->col_nullable_dev, n_cols, k,
+                            sec.hier ? k : k + sec.n_lookup,
+                            sec.hier || sec.cols_contig, sec.winners,
                             sec.tile_counts, sec.tile_offsets, n_tiles_eff,
                             PMH_TILE_ROWS, sec.total_dev, p->out_ptrs_dev,
                             p->out_valid_dev, st);
