@@ -394,6 +394,20 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
                            int64_t n_queries, int32_t *out_level,
                            int64_t *out_row);
 
+/* The merge-path partition on its own: k runs of ascending unique keys
+ * (keys[r] holds lens[r] elements of key_width 4 = int32 or 8 = int64; an
+ * empty run may pass a null pointer). cuts_out receives n_bounds * k entries,
+ * n_bounds = ceil(total / tile_rows) + 1: cuts_out[b * k + r] is the number
+ * of run r's rows among the first min(b * tile_rows, total) rows ordered by
+ * (key, run index). mode 0 walks the shared search core (partition_core.h)
+ * on the host, bound by bound; mode 1 copies the runs to the device, calls
+ * pmh_launch_partition the way pmh_read_next does and copies the cuts back —
+ * only the partition kernels run. Returns 0, or -1 with pmh_last_error()
+ * set. */
+int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
+                        int key_width, int64_t tile_rows, int mode,
+                        int32_t *cuts_out);
+
 /* Parse one JSON number the way the plan descriptor's numbers are parsed
  * (minKey/maxKey, rowCount, integer filter literals): a token without '.',
  * 'e' or 'E' is an exact int64, a fractional token rounds to nearest, an

@@ -23,6 +23,7 @@
 
 #include "kernels.h"
 #include "lookup_core.h"
+#include "partition_core.h"
 #include "zstd_core.h"
 
 #define DEV __device__ __forceinline__
@@ -56,44 +57,24 @@ DEV int64_t key_at(uint64_t addr, int64_t idx, int es) {
                                                                  idx * 4);
 }
 
-// Lockstep multi-run lower/upper bound: runs the k binary searches together
-// so their probe loads issue back-to-back each step (8-16x memory-level
-// parallelism vs sequential searches — the partition kernel was 83%
-// latency-parked on serial probes, profiles/r01_c2_pmc.md). Arrays are
-// indexed only by the unrolled compile-time r, so they stay in registers.
-// le=true: first index with ukey > v; le=false: first index with ukey >= v.
-template <bool LE, int KM>
-DEV void bound_multi(const uint64_t *addr, const int64_t *lo_in,
-                     const int64_t *hi_in, int k, int kes, uint64_t v,
-                     int64_t *out) {
-    int64_t lo[KM], hi[KM];
+// The lockstep multi-run search (ppc_bound_multi), the edge-key and
+// tie-take helpers and the per-bound refine routine live in
+// partition_core.h, shared with the host mode of pmh_debug_partition.
+
+// Run addresses and 32-bit lengths of a KM-wide instantiation: slots r >= k
+// re-read run 0 and become empty runs, so the loads carry no branch.
+template <int KM>
+DEV void partition_runs(const DevCol *__restrict__ keys,
+                        const int64_t *__restrict__ lens, int k,
+                        uint64_t *addr, uint32_t *len) {
 #pragma unroll
     for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        lo[r] = lo_in[r];
-        hi[r] = hi_in[r];
-    }
-    bool any = true;
-    while (any) {
-        any = false;
-#pragma unroll
-        for (int r = 0; r < KM; r++) {
-            if (r >= k) continue;
-            if (lo[r] < hi[r]) {
-                int64_t mid = lo[r] + ((hi[r] - lo[r]) >> 1);
-                uint64_t kk = ukey(key_at(addr[r], mid, kes));
-                bool go = LE ? (kk <= v) : (kk < v);
-                if (go) lo[r] = mid + 1;
-                else hi[r] = mid;
-                any |= lo[r] < hi[r];
-            }
-        }
+        const int rr = r < k ? r : 0;
+        addr[r] = keys[rr].addr0;
+        len[r] = (uint32_t)lens[rr];
     }
 #pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        out[r] = lo[r];
-    }
+    for (int r = 0; r < KM; r++) len[r] = r < k ? len[r] : 0u;
 }
 
 // --------------------------------------------------------- k_partition_wave
@@ -102,16 +83,18 @@ DEV void bound_multi(const uint64_t *addr, const int64_t *lo_in,
 // round the 64 lanes probe 64 evenly spaced pivots of the remaining key
 // domain (each lane runs the lockstep multi-run count for its pivot), a
 // ballot picks the bracketing pair, and domain + per-run windows narrow
-// ~65x. Exact counts, so the cuts are IDENTICAL to k_partition's — but the
-// dependent-load chain is ~4 rounds x log2(window) instead of ~36 x
-// log2(window): the partition wall-clock is one latency chain, and this
-// cuts it ~5x. Validated against a brute-force model on randomized runs
-// (tests/test_tile_algorithm.py + the CPU prototype in git history).
-template <int KM>
-__global__ void k_partition_wave(const DevCol *keys, const int64_t *lens,
-                                 int k, int64_t tile_rows, int64_t n_bounds,
-                                 int64_t total_rows, int64_t stride,
-                                 int32_t *cuts) {
+// ~65x. Exact counts, so the cuts follow the contract in partition_core.h.
+// The dependent-load chain is one round trip per search step: about
+// log65(key span) rounds, each with log2(widest window) steps, every step
+// probing all runs at once (at 8 x 10M rows: 5 rounds, ~61 steps, plus 2
+// trips of setup and 2 of finish). Validated against a brute-force model on
+// randomized runs (tests/test_partition_*.py, tests/test_tile_algorithm.py).
+template <int KM, int ES>
+DEV void partition_wave_body(const DevCol *__restrict__ keys,
+                             const int64_t *__restrict__ lens, int k,
+                             int64_t tile_rows, int64_t n_bounds,
+                             int64_t total_rows, int64_t stride,
+                             int32_t *cuts) {
     // stride > 1: coarse pass of the two-level partition — bounds
     // {0, stride, 2*stride, ...} u {n_bounds-1}; interior bounds follow in
     // k_partition_refine with windows clamped by the enclosing coarse cuts
@@ -127,34 +110,26 @@ __global__ void k_partition_wave(const DevCol *keys, const int64_t *lens,
     int64_t D = b * tile_rows;
     if (D > total_rows) D = total_rows;
     uint64_t addr[KM];
-    int64_t wlo[KM], whi[KM], pos[KM];
-    const int kes = keys[0].esize;
-#pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        addr[r] = keys[r].addr0;
-        wlo[r] = 0;
-        whi[r] = lens[r];
-    }
+    uint32_t len[KM], wlo[KM], whi[KM], pos[KM];
+    partition_runs<KM>(keys, lens, k, addr, len);
     if (D == 0 || D >= total_rows) {
         if (lane == 0) {
 #pragma unroll
             for (int r = 0; r < KM; r++) {
                 if (r >= k) continue;
-                cuts[b * k + r] = D == 0 ? 0 : (int32_t)lens[r];
+                cuts[b * k + r] = D == 0 ? 0 : (int32_t)len[r];
             }
         }
         return;
     }
-    uint64_t klo = ~0ull, khi = 0;
+    ppc_safe_addrs<KM>(addr, len);  // 0 < D < total: a non-empty run exists
 #pragma unroll
     for (int r = 0; r < KM; r++) {
-        if (r >= k || whi[r] == 0) continue;
-        uint64_t lo_k = ukey(key_at(addr[r], 0, kes));
-        uint64_t hi_k = ukey(key_at(addr[r], whi[r] - 1, kes));
-        if (lo_k < klo) klo = lo_k;
-        if (hi_k > khi) khi = hi_k;
+        wlo[r] = 0;
+        whi[r] = len[r];
     }
+    uint64_t klo, khi;
+    ppc_window_keys<ES, KM>(addr, wlo, whi, &klo, &khi);
     while (klo < khi) {
         const uint64_t span = khi - klo;
         uint64_t pv;
@@ -167,13 +142,10 @@ __global__ void k_partition_wave(const DevCol *keys, const int64_t *lens,
             pv = klo + q * (uint64_t)(lane + 1) +
                  (rm * (uint64_t)(lane + 1)) / 65;
         }
-        bound_multi<true, KM>(addr, wlo, whi, k, kes, pv, pos);
+        ppc_bound_multi<true, ES, KM>(addr, wlo, whi, pv, pos);
         int64_t cnt = 0;
 #pragma unroll
-        for (int r = 0; r < KM; r++) {
-            if (r >= k) continue;
-            cnt += pos[r];
-        }
+        for (int r = 0; r < KM; r++) cnt += pos[r];
         const uint64_t ge = __ballot(cnt >= D);
         const int f = ge ? (int)(__ffsll((unsigned long long)ge) - 1) : 64;
         const int fc = f < 64 ? f : 63;   // lane holding the new upper
@@ -185,51 +157,55 @@ __global__ void k_partition_wave(const DevCol *keys, const int64_t *lens,
         else { klo = pv_m + 1; khi = pv_f; }
 #pragma unroll
         for (int r = 0; r < KM; r++) {
-            if (r >= k) continue;
-            const int64_t pf = __shfl(pos[r], fc, 64);
-            const int64_t pm = __shfl(pos[r], fm, 64);
+            const uint32_t pf = __shfl(pos[r], fc, 64);
+            const uint32_t pm = __shfl(pos[r], fm, 64);
             if (f == 64) wlo[r] = pf;
             else if (f == 0) whi[r] = pf;
             else { wlo[r] = pm; whi[r] = pf; }
         }
     }
-    // klo == v*: identical tie-take finish to k_partition (redundant across
-    // lanes; lane 0 stores)
-    bound_multi<false, KM>(addr, wlo, whi, k, kes, klo, pos);
-    int64_t base = 0;
-#pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        base += pos[r];
-    }
-    int64_t t = D - base;
+    // klo == v*: tie-take finish (redundant across lanes; lane 0 stores)
+    ppc_tie_finish<ES, KM>(addr, len, wlo, whi, klo, D, pos);
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < KM; r++) {
             if (r >= k) continue;
-            int64_t c = pos[r];
-            bool has =
-                (c < lens[r]) && (ukey(key_at(addr[r], c, kes)) == klo);
-            if (t > 0 && has) { c++; t--; }
-            cuts[b * k + r] = (int32_t)c;
+            cuts[b * k + r] = (int32_t)pos[r];
         }
     }
+}
+
+// (launch bounds = the launcher's block sizes: the default bound of 1024
+// threads caps a kernel at 128 VGPRs, which KM >= 16 does not fit in)
+template <int KM>
+__launch_bounds__(256) __global__
+void k_partition_wave(const DevCol *__restrict__ keys,
+                      const int64_t *__restrict__ lens, int k,
+                      int64_t tile_rows, int64_t n_bounds, int64_t total_rows,
+                      int64_t stride, int32_t *cuts) {
+    // the key width is uniform across runs: decide it once for the whole body
+    if (keys[0].esize == 8)
+        partition_wave_body<KM, 8>(keys, lens, k, tile_rows, n_bounds,
+                                   total_rows, stride, cuts);
+    else
+        partition_wave_body<KM, 4>(keys, lens, k, tile_rows, n_bounds,
+                                   total_rows, stride, cuts);
 }
 
 // ------------------------------------------------------- k_partition_refine
 //
 // Level 2 of the two-level partition: each interior bound bisects inside
-// the windows of its enclosing coarse cuts. Correct because a coarse cut
-// is two-sided: every element below it keys <= its pivot and the pivot
-// keys of bounds >= tile_rows ranks apart differ strictly (an equal-key
-// group has <= k << tile_rows members, one per run), so no element outside
-// the window can tie with any probed pivot in a way that changes a count
-// comparison.
-template <int KM>
-__global__ void k_partition_refine(const DevCol *keys, const int64_t *lens,
-                                   int k, int64_t tile_rows,
-                                   int64_t n_bounds, int64_t total_rows,
-                                   int64_t G, int32_t *cuts) {
+// the windows of its enclosing coarse cuts (ppc_refine_bound). Correct
+// because a coarse cut is two-sided: every element below it keys <= its
+// pivot and the pivot keys of bounds >= tile_rows ranks apart differ
+// strictly (an equal-key group has <= k << tile_rows members, one per run),
+// so no element outside the window can tie with any probed pivot in a way
+// that changes a count comparison.
+template <int KM, int ES>
+DEV void partition_refine_body(const DevCol *__restrict__ keys,
+                               const int64_t *__restrict__ lens, int k,
+                               int64_t tile_rows, int64_t n_bounds,
+                               int64_t G, int32_t *cuts) {
     int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_bounds - 1) return;
     if (b % G == 0) return;  // coarse pass computed it
@@ -238,71 +214,25 @@ __global__ void k_partition_refine(const DevCol *keys, const int64_t *lens,
     int64_t g1 = g0 + G;
     if (g1 > n_bounds - 1) g1 = n_bounds - 1;
     uint64_t addr[KM];
-    int64_t wlo[KM], whi[KM], pos[KM];
-    const int kes = keys[0].esize;
-    uint64_t klo = ~0ull, khi = 0;
-#pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        addr[r] = keys[r].addr0;
-        wlo[r] = cuts[g0 * k + r];
-        whi[r] = cuts[g1 * k + r];
-        if (wlo[r] < whi[r]) {
-            uint64_t a = ukey(key_at(addr[r], wlo[r], kes));
-            uint64_t z = ukey(key_at(addr[r], whi[r] - 1, kes));
-            if (a < klo) klo = a;
-            if (z > khi) khi = z;
-        }
-    }
-    if (khi < klo) {  // every window empty: the coarse cuts already sum to D
-#pragma unroll
-        for (int r = 0; r < KM; r++) {
-            if (r >= k) continue;
-            cuts[b * k + r] = (int32_t)wlo[r];
-        }
-        return;
-    }
-    while (klo < khi) {
-        uint64_t mid = klo + ((khi - klo) >> 1);
-        bound_multi<true, KM>(addr, wlo, whi, k, kes, mid, pos);
-        int64_t cnt = 0;
-#pragma unroll
-        for (int r = 0; r < KM; r++) {
-            if (r >= k) continue;
-            cnt += pos[r];
-        }
-        if (cnt >= D) {
-            khi = mid;
-#pragma unroll
-            for (int r = 0; r < KM; r++) {
-                if (r >= k) continue;
-                whi[r] = pos[r];
-            }
-        } else {
-            klo = mid + 1;
-#pragma unroll
-            for (int r = 0; r < KM; r++) {
-                if (r >= k) continue;
-                wlo[r] = pos[r];
-            }
-        }
-    }
-    bound_multi<false, KM>(addr, wlo, whi, k, kes, klo, pos);
-    int64_t base = 0;
-#pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        base += pos[r];
-    }
-    int64_t t = D - base;
-#pragma unroll
-    for (int r = 0; r < KM; r++) {
-        if (r >= k) continue;
-        int64_t c = pos[r];
-        bool has = (c < lens[r]) && (ukey(key_at(addr[r], c, kes)) == klo);
-        if (t > 0 && has) { c++; t--; }
-        cuts[b * k + r] = (int32_t)c;
-    }
+    uint32_t len[KM];
+    partition_runs<KM>(keys, lens, k, addr, len);
+    ppc_safe_addrs<KM>(addr, len);
+    ppc_refine_bound<ES, KM>(addr, len, k, D, cuts + g0 * k, cuts + g1 * k,
+                             cuts + b * k);
+}
+
+template <int KM>
+__launch_bounds__(128) __global__
+void k_partition_refine(const DevCol *__restrict__ keys,
+                        const int64_t *__restrict__ lens, int k,
+                        int64_t tile_rows, int64_t n_bounds,
+                        int64_t total_rows, int64_t G, int32_t *cuts) {
+    if (keys[0].esize == 8)
+        partition_refine_body<KM, 8>(keys, lens, k, tile_rows, n_bounds, G,
+                                     cuts);
+    else
+        partition_refine_body<KM, 4>(keys, lens, k, tile_rows, n_bounds, G,
+                                     cuts);
 }
 
 
@@ -4728,15 +4658,28 @@ hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
                                 int64_t total_rows, int32_t *cuts,
                                 hipStream_t stream) {
     // k <= 8 two-level: wave-coarse cuts every PMH_COARSE_G tiles (64-ary
-    // domain search, ~4 probe rounds deep), then windowed refine for the
+    // domain search, ~5 probe rounds deep), then windowed refine for the
     // interior bounds (probes confined to the enclosing coarse windows).
-    // k > 8: the per-lane window state of the wave kernel spills at KM >= 16
-    // and measured SLOWER than one-level bisection (16x20M: 3.9ms two-level
-    // vs 3.2ms one-level, same box — DESIGN.md §7), so seed the endpoints
-    // and run the refine kernel with a single full-width window per bound.
-    const bool two_level = k <= 8;
+    // k > 8: seed the endpoints and run the refine kernel with a single
+    // full-width window per bound. Two-level measured SLOWER there, before
+    // the lockstep search (16x20M: 3.9 ms two-level vs 3.2 one-level, the
+    // wave kernel's 64-bit per-lane state spilled at KM >= 16) and after it
+    // (no scratch at any KM: 3.04 ms two-level vs 1.35 one-level, same box —
+    // DESIGN.md §7): the wave kernel's time is its probe traffic, 64 pivots
+    // x k runs per step, and that doubles with k.
+    // PMH_PART_G (profiling only, read per launch): a coarse stride >= 1
+    // forces the two-level scheme with that stride for every k.
+    int64_t coarse_g = PMH_COARSE_G;
+    bool two_level = k <= 8;
+    if (const char *e = getenv("PMH_PART_G")) {
+        const int64_t g = atoll(e);
+        if (g >= 1 && g <= 4096) {
+            coarse_g = g;
+            two_level = true;
+        }
+    }
     const int64_t G = two_level
-                          ? (n_bounds > PMH_COARSE_G + 1 ? PMH_COARSE_G : 1)
+                          ? (n_bounds > coarse_g + 1 ? coarse_g : 1)
                           : (n_bounds > 1 ? n_bounds - 1 : 1);
     const int64_t n_coarse = (n_bounds - 2) / G + 2;  // {0,G,..} u {last}
     int cblocks = (int)((n_coarse + 3) / 4);  // one wave per coarse bound

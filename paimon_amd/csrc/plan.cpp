@@ -32,6 +32,7 @@
 #include "orc_meta.h"
 #include "parquet_meta.h"
 #include "parquet_write.h"
+#include "partition_core.h"
 
 #include <dlfcn.h>
 
@@ -6035,6 +6036,103 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
         }
     }
     return 0;
+}
+
+int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
+                        int key_width, int64_t tile_rows, int mode,
+                        int32_t *cuts_out) {
+    if (k < 1 || k > PMH_MAX_RUNS || !keys || !lens || !cuts_out ||
+        (key_width != 4 && key_width != 8) || tile_rows < 1 ||
+        (mode != 0 && mode != 1)) {
+        set_error("pmh_debug_partition: bad arguments (1..%d runs, key_width "
+                  "4|8, tile_rows >= 1, mode 0|1)", PMH_MAX_RUNS);
+        return -1;
+    }
+    int64_t total = 0;
+    for (int r = 0; r < k; r++) {
+        if (lens[r] < 0 || lens[r] >= ((int64_t)1 << PMH_ROW_BITS) ||
+            (lens[r] > 0 && !keys[r])) {
+            set_error("pmh_debug_partition: run %d is malformed", r);
+            return -1;
+        }
+        total += lens[r];
+    }
+    const int64_t n_bounds = (total + tile_rows - 1) / tile_rows + 1;
+    if (mode == 0) {
+        // the launcher's level rule (pmh_launch_partition)
+        const int64_t G = k <= 8 ? (n_bounds > PMH_COARSE_G + 1 ? PMH_COARSE_G
+                                                                 : 1)
+                                 : (n_bounds > 1 ? n_bounds - 1 : 1);
+        static_assert(PPC_MAX_RUNS == PMH_MAX_RUNS, "widest instantiation");
+        ppc_host_partition(k, keys, lens, key_width, tile_rows, n_bounds,
+                           total, G, cuts_out);
+        return 0;
+    }
+    // device: the runs as staged columns, then exactly pmh_read_next's call
+    constexpr int GUARD = 64;  // sentinel words behind the cuts
+    const size_t n_cuts = (size_t)n_bounds * k;
+    std::vector<void *> bufs;
+    auto dalloc = [&](size_t n) -> void * {
+        void *p = nullptr;
+        if (hipMalloc(&p, n ? n : 8) != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        return p;
+    };
+    int rc = -1;
+    do {
+        std::vector<DevCol> cols(k);
+        bool ok = true;
+        for (int r = 0; r < k && ok; r++) {
+            DevCol c{};
+            c.n_pages = 1;
+            c.esize = key_width;
+            if (lens[r] > 0) {  // an empty run keeps a null address
+                const size_t nb = (size_t)lens[r] * key_width;
+                void *d = dalloc(nb);
+                ok = d && hipMemcpy(d, keys[r], nb, hipMemcpyHostToDevice) ==
+                              hipSuccess;
+                c.addr0 = (uint64_t)(uintptr_t)d;
+            }
+            cols[r] = c;
+        }
+        DevCol *d_cols = (DevCol *)dalloc(k * sizeof(DevCol));
+        int64_t *d_lens = (int64_t *)dalloc(k * 8);
+        int32_t *d_cuts = (int32_t *)dalloc((n_cuts + GUARD) * 4);
+        if (!ok || !d_cols || !d_lens || !d_cuts ||
+            hipMemcpy(d_cols, cols.data(), k * sizeof(DevCol),
+                      hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_lens, lens, k * 8, hipMemcpyHostToDevice) !=
+                hipSuccess ||
+            hipMemset(d_cuts, 0x5a, (n_cuts + GUARD) * 4) != hipSuccess) {
+            set_error("pmh_debug_partition: device staging failed");
+            break;
+        }
+        hipError_t e = pmh_launch_partition(d_cols, d_lens, k, tile_rows,
+                                            n_bounds, total, d_cuts, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            set_error("pmh_debug_partition: partition kernels: %s",
+                      hipGetErrorString(e));
+            break;
+        }
+        std::vector<int32_t> host(n_cuts + GUARD);
+        if (hipMemcpy(host.data(), d_cuts, host.size() * 4,
+                      hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("pmh_debug_partition: D2H failed");
+            break;
+        }
+        bool clean = true;
+        for (int i = 0; i < GUARD; i++)
+            clean &= host[n_cuts + i] == 0x5a5a5a5a;
+        if (!clean) {
+            set_error("pmh_debug_partition: a kernel wrote outside its cuts");
+            break;
+        }
+        memcpy(cuts_out, host.data(), n_cuts * 4);
+        rc = 0;
+    } while (false);
+    for (void *p : bufs) (void)hipFree(p);
+    return rc;
 }
 
 // The plan descriptor's number rule, exposed on its own: `text` goes through

@@ -509,6 +509,40 @@ def debug_lookup_probe(levels, queries):
     return out_level, out_row
 
 
+PARTITION_HOST = 0
+PARTITION_DEVICE = 1
+
+
+def debug_partition(runs, tile_rows, mode=PARTITION_HOST):
+    """Merge-path partition cuts of `runs` (a list of ascending unique key
+    arrays, all int64 or all int32) through pmh_debug_partition: the shared
+    search core on the host (PARTITION_HOST) or the partition kernels alone
+    (PARTITION_DEVICE). Returns an int32 array [n_bounds, k]."""
+    lib = load_lib()
+    dt = np.dtype(runs[0].dtype)
+    if dt not in (np.dtype(np.int64), np.dtype(np.int32)):
+        raise ValueError("keys must be int64 or int32")
+    ks = [np.ascontiguousarray(a, dtype=dt) for a in runs]
+    k = len(ks)
+    total = sum(len(a) for a in ks)
+    n_bounds = (total + tile_rows - 1) // tile_rows + 1
+    ptrs = (ctypes.c_void_p * k)(
+        *[a.ctypes.data if len(a) else None for a in ks])
+    lens = (ctypes.c_int64 * k)(*[len(a) for a in ks])
+    cuts = np.empty((n_bounds, k), dtype=np.int32)
+    lib.pmh_debug_partition.restype = ctypes.c_int
+    lib.pmh_debug_partition.argtypes = [
+        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
+    rc = lib.pmh_debug_partition(
+        k, ptrs, lens, dt.itemsize, tile_rows, mode,
+        cuts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return cuts
+
+
 class Session:
     def __init__(self, device=0):
         self.lib = load_lib()
