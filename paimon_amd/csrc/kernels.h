@@ -9,6 +9,7 @@
 #include "bits_core.h"
 #include "orc_decimal_core.h"
 #include "orc_timestamp_core.h"
+#include "stream_core.h"
 
 namespace pmh {
 
@@ -56,84 +57,8 @@ struct DevCol {
     int32_t esize;  // element size in bytes (stored width)
 };
 
-// Host-prescanned RLE/bit-packed work unit (split at group boundaries).
-struct RleChunk {
-    uint64_t src;       // device pointer to first packed group (kind 1)
-    int64_t out_start;  // output element index
-    int32_t count;
-    int32_t kind;       // 0 = RLE run, 1 = bit-packed groups
-    uint32_t value;     // RLE literal (kind 0)
-    int32_t bit_width;  // per-page bit width (dict-id streams vary per page)
-    int64_t aux;        // def-level streams: dense (non-null) values before
-                        // this chunk within its (run, column)
-    // absolute device addresses (patched at staging finalize) so decode
-    // chunks from every (run, column) batch into ONE launch:
-    uint64_t out_addr;    // positioned column values
-    uint64_t valid_addr;  // byte validity
-    uint64_t dense_addr;  // dense (non-null) values
-    int32_t esize;
-    int32_t _pad2;
-};
-
-// Host-prescanned ORC RLEv2 / byte-RLE work unit (one run per chunk; runs
-// are <= 512 values and byte-aligned). Restates the ORC v1 spec RLEv2 as
-// consumed by the reference through orc-core 1.9.8.
-struct Rlev2Chunk {
-    uint64_t src;        // packed values (byte-aligned within DATA stream)
-    int64_t out_start;   // dense output element index
-    int32_t count;
-    uint8_t kind;        // 0 SHORT_REPEAT, 1 DIRECT, 2 PATCHED_BASE,
-                         // 3 DELTA, 4 BYTE_RUN, 5 BYTE_LITERAL
-    uint8_t width;       // packed bit width (0 = fixed-delta / none)
-    uint8_t is_signed;   // zigzag-decode DIRECT/SHORT_REPEAT values
-    uint8_t out_esize;   // 4 or 8
-    int64_t base;        // SR/BYTE_RUN: value; DELTA/PATCHED: base
-    int64_t delta;       // DELTA: delta base (sign = direction)
-    uint64_t patch_src;  // PATCHED: packed patch entries
-    uint16_t patch_pl;   // PATCHED: number of patch entries
-    uint8_t patch_pw;    // PATCHED: patch value bits (decoded)
-    uint8_t patch_pgw;   // PATCHED: gap bits
-    uint8_t patch_cfb;   // PATCHED: packed entry bits
-    uint8_t dense_target;  // 0: contig (positioned); 1: dense buffer
-                           // (PRESENT scatter follows); 2: the (run,
-                           // column)'s int32 decimal-scale scratch
-                           // (out_start = scratch index); 3: its uint64
-                           // timestamp-nanos scratch (likewise)
-    uint8_t _pad[2];
-    uint64_t out_addr;     // absolute output base (patched at finalize)
-};
-
-// Host-prescanned DELTA_BINARY_PACKED work unit: one parquet delta BLOCK
-// (VectorizedDeltaBinaryPackedReader.java; parquet-format encodings.md):
-// per block, <= 8 miniblocks of vpm values each, bit widths packed into
-// `widths` (8 bits each), LSB-first bit packing. Blocks chain: the value
-// base entering block b = page first_value + sum of all prior blocks'
-// delta sums — computed on device (k_delta_sum + per-stream scan).
-struct DeltaChunk {
-    uint64_t src;       // packed miniblock data (byte-aligned)
-    uint64_t out_addr;  // absolute output base (patched at finalize)
-    int64_t out_start;  // output index of this block's FIRST delta value
-    int64_t min_delta;
-    int32_t count;      // real delta values in this block
-    int32_t stream;     // delta-stream index (for base resolution)
-    uint64_t widths;    // miniblock bit widths, 8 bits each
-    int16_t vpm;        // values per miniblock
-    int16_t n_mini;
-    int32_t out_esize;  // 4 or 8
-};
-
-// One DELTA stream (= one column chunk's page chain? no — one PAGE: pages
-// are self-contained): chunk range + the page's first value and where it
-// lands in the output.
-struct DeltaStream {
-    int64_t chunk_lo;
-    int64_t chunk_hi;
-    int64_t first;       // header first value = output element out0
-    int64_t out0;        // output index of the first value
-    uint64_t out_addr;   // absolute output base (patched at finalize)
-    int32_t out_esize;
-    int32_t _pad;
-};
+// RleChunk, Rlev2Chunk, DeltaChunk, DeltaStream: stream_core.h (the host
+// walks that fill them live there).
 
 extern "C" {
 

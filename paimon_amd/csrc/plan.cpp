@@ -898,8 +898,6 @@ static int dtype_stored_esize(int dt) {
     return 0;
 }
 
-static inline int popcount8(uint8_t b) { return __builtin_popcount(b); }
-
 static int expected_phys(int dtype) {
     switch (dtype) {
     case PMH_DT_INT8:
@@ -1001,325 +999,6 @@ static bool check_bool_page(const std::string &path, const ColSpec &cs,
     return false;
 }
 
-// Walk a def-level stream (bit width 1): emit device work chunks with
-// running dense offsets (aux) and report the number of non-null values.
-// src offsets are RELATIVE to the (run,col) levels buffer (rel_base =
-// offset of this stream within it); patched to device addresses at upload.
-static bool prescan_def(const uint8_t *s, int64_t len, int64_t n,
-                        int64_t out_row0, int64_t rel_base,
-                        int64_t *dense_before, std::vector<RleChunk> &out) {
-    int64_t p = 0, cnt = 0;
-    // one wave per chunk in k_level_scatter: chunk size bounds the serial
-    // 64-value passes per wave
-    const int64_t MAX_CHUNK = 512;
-    while (cnt < n) {
-        if (p >= len) {
-            set_error("def-level stream overrun");
-            return false;
-        }
-        uint64_t header = 0;
-        int shift = 0;
-        for (;;) {
-            uint8_t b = s[p++];
-            header |= (uint64_t)(b & 0x7F) << shift;
-            if (!(b & 0x80)) break;
-            shift += 7;
-        }
-        if ((header & 1) == 0) {
-            int64_t count = std::min<int64_t>((int64_t)(header >> 1), n - cnt);
-            uint8_t v = s[p++] & 1;
-            for (int64_t off = 0; off < count; off += MAX_CHUNK) {
-                RleChunk c{};
-                c.kind = 0;
-                c.value = v;
-                c.out_start = out_row0 + cnt + off;
-                c.count = (int32_t)std::min<int64_t>(MAX_CHUNK, count - off);
-                c.bit_width = 1;
-                c.aux = *dense_before + (v ? off : 0);
-                out.push_back(c);
-            }
-            if (v) *dense_before += count;
-            cnt += count;
-        } else {
-            int64_t groups = (int64_t)(header >> 1);
-            int64_t vals = std::min<int64_t>(groups * 8, n - cnt);
-            int64_t voff = 0;
-            while (voff < vals) {
-                int64_t take = std::min<int64_t>(MAX_CHUNK, vals - voff);
-                RleChunk c{};
-                c.kind = 1;
-                c.src = (uint64_t)(rel_base + p + voff / 8);
-                c.out_start = out_row0 + cnt + voff;
-                c.count = (int32_t)take;
-                c.bit_width = 1;
-                c.aux = *dense_before;
-                out.push_back(c);
-                // advance dense count by the set bits in this chunk
-                for (int64_t i = 0; i < take; i += 8) {
-                    uint8_t b = s[p + (voff + i) / 8];
-                    int64_t rem = take - i;
-                    uint8_t mask =
-                        rem >= 8 ? 0xFF : (uint8_t)((1u << rem) - 1);
-                    *dense_before += popcount8(b & mask);
-                }
-                voff += take;
-            }
-            p += groups;
-            cnt += vals;
-        }
-    }
-    return true;
-}
-
-// Walk an RLE/bit-packed def-level stream (bit width 1) and report whether
-// any zero (null) occurs among the first n values.
-static bool def_levels_have_nulls(const uint8_t *s, int64_t len, int64_t n) {
-    int64_t p = 0, cnt = 0;
-    while (cnt < n && p < len) {
-        uint64_t header = 0;
-        int shift = 0;
-        for (;;) {
-            if (p >= len) return true;  // malformed: treat as nulls
-            uint8_t b = s[p++];
-            header |= (uint64_t)(b & 0x7F) << shift;
-            if (!(b & 0x80)) break;
-            shift += 7;
-        }
-        if ((header & 1) == 0) {
-            int64_t count = (int64_t)(header >> 1);
-            if (p >= len) return true;
-            uint8_t v = s[p++];
-            if (count > n - cnt) count = n - cnt;
-            if (v == 0 && count > 0) return true;
-            cnt += count;
-        } else {
-            int64_t groups = (int64_t)(header >> 1);
-            for (int64_t g = 0; g < groups && cnt < n; g++) {
-                if (p >= len) return true;
-                uint8_t v = s[p++];
-                int64_t take = std::min<int64_t>(8, n - cnt);
-                uint8_t mask = take >= 8 ? 0xFF : (uint8_t)((1u << take) - 1);
-                if ((v & mask) != mask) return true;
-                cnt += take;
-            }
-        }
-    }
-    return cnt < n ? true : false;
-}
-
-// Prescan an RLE stream into device work chunks (splitting long runs).
-static bool prescan_rle(const uint8_t *s, int64_t len, int bit_width,
-                        int64_t n, int64_t out_base, uint64_t dev_base,
-                        int64_t host_off, std::vector<RleChunk> &out) {
-    int64_t p = 0, cnt = 0;
-    int byte_width = (bit_width + 7) / 8;
-    const int64_t MAX_CHUNK = 16384;
-    while (cnt < n) {
-        if (p >= len) {
-            set_error("RLE stream overrun");
-            return false;
-        }
-        uint64_t header = 0;
-        int shift = 0;
-        for (;;) {
-            uint8_t b = s[p++];
-            header |= (uint64_t)(b & 0x7F) << shift;
-            if (!(b & 0x80)) break;
-            shift += 7;
-        }
-        if ((header & 1) == 0) {
-            int64_t count = std::min<int64_t>((int64_t)(header >> 1), n - cnt);
-            uint32_t v = 0;
-            for (int i = 0; i < byte_width; i++) v |= (uint32_t)s[p + i] << (8 * i);
-            p += byte_width;
-            for (int64_t off = 0; off < count; off += MAX_CHUNK) {
-                RleChunk c{};
-                c.kind = 0;
-                c.value = v;
-                c.out_start = out_base + cnt + off;
-                c.count = (int32_t)std::min<int64_t>(MAX_CHUNK, count - off);
-                c.bit_width = bit_width;
-                out.push_back(c);
-            }
-            cnt += count;
-        } else {
-            int64_t groups = (int64_t)(header >> 1);
-            int64_t vals = std::min<int64_t>(groups * 8, n - cnt);
-            // split at group boundaries
-            for (int64_t voff = 0; voff < vals; voff += MAX_CHUNK) {
-                RleChunk c{};
-                c.kind = 1;
-                c.src = dev_base + (uint64_t)(host_off + p) +
-                        (uint64_t)((voff / 8) * bit_width);
-                c.out_start = out_base + cnt + voff;
-                c.count = (int32_t)std::min<int64_t>(MAX_CHUNK, vals - voff);
-                c.bit_width = bit_width;
-                out.push_back(c);
-            }
-            p += groups * bit_width;
-            cnt += vals;
-        }
-    }
-    return true;
-}
-
-
-// Prescan one DELTA_BINARY_PACKED page (VectorizedDeltaBinaryPackedReader
-// .java / parquet-format Encodings.md): header <block_size><miniblocks_per_
-// block><total_count><first zigzag>, then blocks of [min_delta zigzag]
-// [miniblock widths][packed miniblocks]. Each PAGE is self-contained (its
-// own first value), so it forms one DeltaStream; each block becomes one
-// DeltaChunk. Miniblocks holding no real values carry a width byte but no
-// data (their widths zero out in the packed u64 so device byte offsets
-// skip nothing); partially-filled miniblocks are stored in full.
-// Host DELTA_BINARY_PACKED decode of one complete stream (parquet
-// delta-encoding spec; the GPU path decodes these on device — this host
-// version serves DELTA_BYTE_ARRAY string staging, where values intern into
-// the global dictionary anyway). Returns bytes consumed or -1.
-static int64_t host_delta_i64(const uint8_t *pp, int64_t plen,
-                              std::vector<int64_t> &out) {
-    int64_t pos = 0;
-    auto uleb = [&](uint64_t *v) -> bool {
-        *v = 0;
-        int sh = 0;
-        for (;;) {
-            if (pos >= plen) return false;
-            uint8_t b = pp[pos++];
-            *v |= (uint64_t)(b & 0x7f) << sh;
-            if (!(b & 0x80)) return true;
-            sh += 7;
-        }
-    };
-    auto zz = [](uint64_t v) {
-        return (int64_t)(v >> 1) ^ -(int64_t)(v & 1);
-    };
-    uint64_t bs, mpb, total, zfirst;
-    if (!uleb(&bs) || !uleb(&mpb) || !uleb(&total) || !uleb(&zfirst))
-        return -1;
-    if (mpb == 0 || bs % mpb != 0) return -1;
-    const int64_t vpm = (int64_t)(bs / mpb);
-    out.clear();
-    out.reserve(total);
-    if (total == 0) return pos;
-    int64_t cur = zz(zfirst);
-    out.push_back(cur);
-    int64_t remaining = (int64_t)total - 1;
-    while (remaining > 0) {
-        uint64_t zmd;
-        if (!uleb(&zmd) || pos + (int64_t)mpb > plen) return -1;
-        int64_t mind = zz(zmd);
-        const uint8_t *widths = pp + pos;
-        pos += mpb;
-        for (uint64_t m = 0; m < mpb && remaining > 0; m++) {
-            int w = widths[m];
-            if (w > 64) return -1;
-            int64_t take = remaining < vpm ? remaining : vpm;
-            if (pos + (vpm * w + 7) / 8 > plen) return -1;
-            for (int64_t j = 0; j < take; j++) {
-                uint64_t d = 0;  // LSB-first bit-packed
-                for (int b = 0; b < w; b++) {
-                    int64_t bit = j * w + b;
-                    d |= (uint64_t)((pp[pos + (bit >> 3)] >> (bit & 7)) & 1)
-                         << b;
-                }
-                cur += mind + (int64_t)d;
-                out.push_back(cur);
-            }
-            pos += (vpm * w + 7) / 8;  // full miniblock advances
-            remaining -= take;
-        }
-    }
-    return pos;
-}
-
-static bool prescan_delta(const uint8_t *pp, int64_t plen, int64_t n_values,
-                          int64_t out_row0, uint64_t dev_base,
-                          int64_t rel_off, uint64_t out_addr, int out_esize,
-                          std::vector<DeltaChunk> &chunks,
-                          std::vector<DeltaStream> &streams,
-                          std::string &err) {
-    int64_t pos = 0;
-    auto uleb = [&](uint64_t *v) -> bool {
-        *v = 0;
-        int sh = 0;
-        for (;;) {
-            if (pos >= plen) return false;
-            uint8_t b = pp[pos++];
-            *v |= (uint64_t)(b & 0x7f) << sh;
-            if (!(b & 0x80)) return true;
-            sh += 7;
-        }
-    };
-    auto zz = [](uint64_t v) {
-        return (int64_t)(v >> 1) ^ -(int64_t)(v & 1);
-    };
-    uint64_t bs, mpb, total, zfirst;
-    if (!uleb(&bs) || !uleb(&mpb) || !uleb(&total) || !uleb(&zfirst)) {
-        err = "delta: truncated header";
-        return false;
-    }
-    if (mpb == 0 || mpb > 8 || bs % mpb != 0) {
-        err = "delta: unsupported miniblock layout (v1: <= 8 per block)";
-        return false;
-    }
-    if ((int64_t)total != n_values) {
-        err = "delta: header count disagrees with page";
-        return false;
-    }
-    const int vpm = (int)(bs / mpb);
-    if (n_values == 0) return true;
-    DeltaStream st{};
-    st.chunk_lo = (int64_t)chunks.size();
-    st.first = zz(zfirst);
-    st.out0 = out_row0;
-    st.out_addr = out_addr;
-    st.out_esize = out_esize;
-    int64_t remaining = n_values - 1;
-    int64_t out_i = out_row0 + 1;
-    while (remaining > 0) {
-        uint64_t zmd;
-        if (!uleb(&zmd) || pos + (int64_t)mpb > plen) {
-            err = "delta: truncated block";
-            return false;
-        }
-        DeltaChunk ch{};
-        ch.min_delta = zz(zmd);
-        ch.vpm = (int16_t)vpm;
-        ch.n_mini = (int16_t)mpb;
-        ch.out_addr = out_addr;
-        ch.out_start = out_i;
-        ch.out_esize = out_esize;
-        ch.count = (int32_t)(remaining < (int64_t)bs ? remaining
-                                                     : (int64_t)bs);
-        int64_t data = 0;
-        for (uint64_t j = 0; j < mpb; j++) {
-            const int w = pp[pos + j];
-            if (w > 64) {
-                err = "delta: miniblock width > 64";
-                return false;
-            }
-            const int64_t real = remaining - (int64_t)j * vpm;
-            if (real > 0) {
-                ch.widths |= (uint64_t)w << (8 * j);
-                data += (int64_t)vpm * w / 8;
-            }
-        }
-        pos += mpb;
-        ch.src = dev_base + (uint64_t)(rel_off + pos);
-        if (pos + data > plen) {
-            err = "delta: truncated miniblocks";
-            return false;
-        }
-        pos += data;
-        chunks.push_back(ch);
-        out_i += ch.count;
-        remaining -= ch.count;
-    }
-    st.chunk_hi = (int64_t)chunks.size();
-    streams.push_back(st);
-    return true;
-}
-
 struct StagedFile {
     std::vector<uint8_t> data;  // whole file (or decompressed payload view)
     bool orc = false;
@@ -1362,418 +1041,6 @@ static bool load_file(const std::string &path, StagedFile &sf) {
 }
 
 // ------------------------------------------------- ORC staging (RLEv2)
-
-// Walk an ORC RLEv2 stream (runs <= 512 values, byte-aligned) and emit one
-// device work chunk per run. dev_base = device address of the uploaded
-// stream bytes; dense0 = dense output offset of this stream's first value.
-// Host RLEv2 decode (UNSIGNED interpretation) — ORC LENGTH / side streams
-// that staging needs on the host (string id-ification). Restates the ORC
-// v1 spec's RLEv2 (same arithmetic as k_rlev2;
-// orc/impl/RunLengthIntegerReaderV2.java is the reference consumer).
-// The spec's 5-bit width code -> bit width table ("fixed bit sizes"): the one
-// copy both the host decoder and the prescan read.
-static const int RLEV2_FBS[32] = {1,  2,  3,  4,  5,  6,  7,  8,
-                                  9,  10, 11, 12, 13, 14, 15, 16,
-                                  17, 18, 19, 20, 21, 22, 23, 24,
-                                  26, 28, 30, 32, 40, 48, 56, 64};
-
-static int rlev2_width(int enc) { return RLEV2_FBS[enc & 31]; }
-
-// Smallest encodable width >= n: PATCHED_BASE packs each (gap, patch) entry
-// at closest_fixed_bits(pgw + pw) bits.
-static int rlev2_closest_fixed_bits(int n) {
-    for (int i = 0; i < 32; i++)
-        if (RLEV2_FBS[i] >= n) return RLEV2_FBS[i];
-    return 64;
-}
-
-// is_signed: SHORT_REPEAT / DIRECT values and the DELTA base are zigzag
-// (signed streams: the ORC TIMESTAMP seconds of the debug entry's host mode);
-// the values then come back as the int64 bit patterns.
-static bool host_rlev2(const uint8_t *s, int64_t len, int64_t n,
-                       bool is_signed, std::vector<uint64_t> &out) {
-    auto unzz = [&](uint64_t v) -> uint64_t {
-        return is_signed ? (v >> 1) ^ (0 - (v & 1)) : v;
-    };
-    out.clear();
-    if (n > 0) out.reserve(n);
-    int64_t p = 0;
-    auto bits_be = [&](int64_t q, int64_t bitpos, int w) -> uint64_t {
-        uint64_t v = 0;
-        for (int i = 0; i < w; i++) {
-            int64_t b = bitpos + i;
-            v = (v << 1) | ((s[q + (b >> 3)] >> (7 - (b & 7))) & 1);
-        }
-        return v;
-    };
-    // n < 0: decode until the stream is exhausted (dictionary LENGTH
-    // streams — the entry count comes from the stream itself)
-    while (n < 0 ? p < len : (int64_t)out.size() < n) {
-        if (p >= len) return false;
-        uint8_t h = s[p];
-        int mode = h >> 6;
-        if (mode == 0) {  // SHORT_REPEAT
-            int w = ((h >> 3) & 7) + 1;
-            int cnt = (h & 7) + 3;
-            if (p + 1 + w > len) return false;
-            uint64_t v = 0;
-            for (int i = 0; i < w; i++) v = (v << 8) | s[p + 1 + i];
-            v = unzz(v);
-            for (int i = 0; i < cnt; i++) out.push_back(v);
-            p += 1 + w;
-        } else if (mode == 1) {  // DIRECT
-            int w = rlev2_width((h >> 1) & 31);
-            if (p + 2 > len) return false;
-            int cnt = (((int)(h & 1)) << 8 | s[p + 1]) + 1;
-            int64_t nbytes = ((int64_t)cnt * w + 7) / 8;
-            if (p + 2 + nbytes > len) return false;
-            for (int i = 0; i < cnt; i++)
-                out.push_back(unzz(bits_be(p + 2, (int64_t)i * w, w)));
-            p += 2 + nbytes;
-        } else if (mode == 2) {  // PATCHED_BASE
-            if (p + 4 > len) return false;
-            int w = rlev2_width((h >> 1) & 31);
-            int cnt = (((int)(h & 1)) << 8 | s[p + 1]) + 1;
-            int bw = ((s[p + 2] >> 5) & 7) + 1;
-            int pw = rlev2_width(s[p + 2] & 31);
-            int pgw = ((s[p + 3] >> 5) & 7) + 1;
-            int pll = s[p + 3] & 31;
-            int64_t q = p + 4;
-            if (q + bw > len || pw + pgw > 64) return false;
-            uint64_t braw = 0;
-            for (int i = 0; i < bw; i++) braw = (braw << 8) | s[q + i];
-            int64_t base = (int64_t)braw;
-            uint64_t sign = 1ull << (bw * 8 - 1);
-            if (braw & sign) base = -(int64_t)(braw & (sign - 1));
-            q += bw;
-            int64_t dbytes = ((int64_t)cnt * w + 7) / 8;
-            int pbits = rlev2_closest_fixed_bits(pgw + pw);
-            int64_t pbytes = ((int64_t)pll * pbits + 7) / 8;
-            if (q + dbytes + pbytes > len) return false;
-            std::vector<uint64_t> vals(cnt);
-            for (int i = 0; i < cnt; i++)
-                vals[i] = bits_be(q, (int64_t)i * w, w);
-            int64_t gap = 0;
-            for (int i = 0; i < pll; i++) {
-                uint64_t e = bits_be(q + dbytes, (int64_t)i * pbits, pbits);
-                uint64_t patch =
-                    e & ((pw >= 64) ? ~0ull : ((1ull << pw) - 1));
-                gap += (int64_t)(e >> pw);
-                if (gap >= cnt) return false;
-                vals[gap] |= patch << w;
-            }
-            for (int i = 0; i < cnt; i++)
-                out.push_back((uint64_t)(base + (int64_t)vals[i]));
-            p = q + dbytes + pbytes;
-        } else {  // DELTA
-            int enc = (h >> 1) & 31;
-            int w = enc == 0 ? 0 : rlev2_width(enc);
-            if (p + 2 > len) return false;
-            int cnt = (((int)(h & 1)) << 8 | s[p + 1]) + 1;
-            int64_t q = p + 2;
-            uint64_t base = 0;  // base: unsigned varint (UNSIGNED streams)
-            int sh = 0;
-            for (;;) {
-                if (q >= len) return false;
-                uint8_t b = s[q++];
-                base |= (uint64_t)(b & 0x7f) << sh;
-                if (!(b & 0x80)) break;
-                sh += 7;
-            }
-            uint64_t zd = 0;  // delta0: signed varint (zigzag)
-            sh = 0;
-            for (;;) {
-                if (q >= len) return false;
-                uint8_t b = s[q++];
-                zd |= (uint64_t)(b & 0x7f) << sh;
-                if (!(b & 0x80)) break;
-                sh += 7;
-            }
-            int64_t d0 = (int64_t)(zd >> 1) ^ -(int64_t)(zd & 1);
-            base = unzz(base);
-            out.push_back(base);
-            int64_t cur = (int64_t)base;
-            if (cnt > 1) {
-                cur += d0;
-                out.push_back((uint64_t)cur);
-            }
-            if (w == 0) {
-                for (int i = 2; i < cnt; i++) {
-                    cur += d0;
-                    out.push_back((uint64_t)cur);
-                }
-            } else {
-                // a run of 1 or 2 values carries no packed deltas
-                int64_t nbytes =
-                    cnt > 2 ? ((int64_t)(cnt - 2) * w + 7) / 8 : 0;
-                if (q + nbytes > len) return false;
-                for (int i = 2; i < cnt; i++) {
-                    int64_t d = (int64_t)bits_be(q, (int64_t)(i - 2) * w, w);
-                    cur += d0 < 0 ? -d : d;
-                    out.push_back((uint64_t)cur);
-                }
-                q += nbytes;
-            }
-            p = q;
-        }
-    }
-    return n < 0 || (int64_t)out.size() >= n;
-}
-
-static bool host_rlev2_u(const uint8_t *s, int64_t len, int64_t n,
-                         std::vector<uint64_t> &out) {
-    return host_rlev2(s, len, n, false, out);
-}
-
-static bool host_rlev2_s(const uint8_t *s, int64_t len, int64_t n,
-                         std::vector<uint64_t> &out) {
-    return host_rlev2(s, len, n, true, out);
-}
-
-static bool prescan_rlev2(const uint8_t *s, int64_t len, int64_t n_values,
-                          int is_signed, int out_esize, int dense_target,
-                          uint64_t dev_base, int64_t dense0,
-                          std::vector<Rlev2Chunk> &out) {
-    const int *fbs = RLEV2_FBS;
-    int64_t p = 0, cnt = 0;
-    // every header byte is checked against len BEFORE it is read
-    auto need = [&](int64_t nbytes) -> bool {
-        if (p + nbytes <= len) return true;
-        set_error("RLEv2 run header truncated");
-        return false;
-    };
-    auto uvarint = [&](bool &ok) -> uint64_t {
-        uint64_t v = 0;
-        int shift = 0;
-        for (;;) {
-            if (p >= len) { ok = false; return 0; }
-            uint8_t b = s[p++];
-            v |= (uint64_t)(b & 0x7F) << shift;
-            if (!(b & 0x80)) return v;
-            shift += 7;
-        }
-    };
-    while (cnt < n_values) {
-        if (p >= len) {
-            set_error("RLEv2 stream overrun");
-            return false;
-        }
-        uint8_t first = s[p++];
-        int enc = (first >> 6) & 3;
-        Rlev2Chunk c{};
-        c.is_signed = (uint8_t)is_signed;
-        c.out_esize = (uint8_t)out_esize;
-        c.dense_target = (uint8_t)dense_target;
-        c.out_start = dense0 + cnt;
-        if (enc == 0) {  // SHORT_REPEAT: host decodes the literal
-            int w = ((first >> 3) & 7) + 1;
-            int rep = (first & 7) + 3;
-            if (!need(w)) return false;
-            uint64_t raw = 0;
-            for (int i = 0; i < w; i++) raw = (raw << 8) | s[p++];
-            c.kind = 0;
-            c.base = is_signed
-                         ? ((int64_t)(raw >> 1) ^ -(int64_t)(raw & 1))
-                         : (int64_t)raw;
-            c.count = rep;
-            cnt += rep;
-        } else if (enc == 1) {  // DIRECT
-            if (!need(1)) return false;
-            int width = fbs[(first >> 1) & 0x1f];
-            int count = (int)(((first & 1) << 8) | s[p++]) + 1;
-            c.kind = 1;
-            c.width = (uint8_t)width;
-            c.count = count;
-            c.src = dev_base + p;
-            p += ((int64_t)count * width + 7) / 8;
-            cnt += count;
-        } else if (enc == 2) {  // PATCHED_BASE
-            if (!need(3)) return false;
-            int width = fbs[(first >> 1) & 0x1f];
-            int count = (int)(((first & 1) << 8) | s[p++]) + 1;
-            uint8_t third = s[p++], fourth = s[p++];
-            int bw = ((third >> 5) & 7) + 1;
-            int pw = fbs[third & 0x1f];
-            int pgw = ((fourth >> 5) & 7) + 1;
-            int pl = fourth & 0x1f;
-            if (!need(bw)) return false;
-            if (pw + pgw > 64) {
-                set_error("RLEv2 patch entry wider than 64 bits");
-                return false;
-            }
-            uint64_t braw = 0;
-            for (int i = 0; i < bw; i++) braw = (braw << 8) | s[p++];
-            uint64_t smask = 1ull << (bw * 8 - 1);
-            c.kind = 2;
-            c.width = (uint8_t)width;
-            c.count = count;
-            c.base = (braw & smask) ? -(int64_t)(braw & ~smask)
-                                    : (int64_t)braw;
-            c.src = dev_base + p;
-            p += ((int64_t)count * width + 7) / 8;
-            int cfb = rlev2_closest_fixed_bits(pw + pgw);
-            c.patch_src = dev_base + p;
-            c.patch_pl = (uint16_t)pl;
-            c.patch_pw = (uint8_t)pw;
-            c.patch_pgw = (uint8_t)pgw;
-            c.patch_cfb = (uint8_t)cfb;
-            p += ((int64_t)pl * cfb + 7) / 8;
-            cnt += count;
-        } else {  // DELTA
-            int wcode = (first >> 1) & 0x1f;
-            int width = wcode == 0 ? 0 : fbs[wcode];
-            if (!need(1)) return false;
-            int count = (int)(((first & 1) << 8) | s[p++]) + 1;
-            bool ok = true;
-            uint64_t braw = uvarint(ok);
-            int64_t base = is_signed
-                               ? ((int64_t)(braw >> 1) ^ -(int64_t)(braw & 1))
-                               : (int64_t)braw;
-            uint64_t draw = uvarint(ok);
-            int64_t delta = (int64_t)(draw >> 1) ^ -(int64_t)(draw & 1);
-            if (!ok) {
-                set_error("RLEv2 delta varint overrun");
-                return false;
-            }
-            c.kind = 3;
-            c.width = (uint8_t)width;
-            c.count = count;
-            c.base = base;
-            c.delta = delta;
-            c.src = dev_base + p;
-            if (width > 0 && count > 2)
-                p += ((int64_t)(count - 2) * width + 7) / 8;
-            cnt += count;
-        }
-        out.push_back(c);
-        if (p > len) {
-            set_error("RLEv2 stream overran its length");
-            return false;
-        }
-    }
-    return true;
-}
-
-// ORC byte-RLE (tinyint columns, e.g. _VALUE_KIND): header h >= 0 -> h+3
-// copies of the next byte; h < 0 -> -h literal bytes.
-static bool prescan_byterle(const uint8_t *s, int64_t len, int64_t n_values,
-                            int out_esize, int dense_target,
-                            uint64_t dev_base, int64_t dense0,
-                            std::vector<Rlev2Chunk> &out) {
-    int64_t p = 0, cnt = 0;
-    while (cnt < n_values) {
-        if (p >= len) {
-            set_error("byte-RLE stream overrun");
-            return false;
-        }
-        int8_t h = (int8_t)s[p++];
-        Rlev2Chunk c{};
-        c.out_esize = (uint8_t)out_esize;
-        c.dense_target = (uint8_t)dense_target;
-        c.out_start = dense0 + cnt;
-        if (h >= 0) {
-            if (p >= len) {
-                set_error("byte-RLE run truncated");
-                return false;
-            }
-            c.kind = 4;
-            c.base = (int8_t)s[p++];
-            c.count = (int32_t)std::min<int64_t>(h + 3, n_values - cnt);
-        } else {
-            c.kind = 5;
-            c.src = dev_base + p;
-            c.count = (int32_t)std::min<int64_t>(-(int64_t)h, n_values - cnt);
-            // the kernel reads c.count literal bytes: they must be there
-            if (p + c.count > len) {
-                set_error("byte-RLE literal truncated");
-                return false;
-            }
-            p += -(int64_t)h;
-        }
-        cnt += c.count;
-        out.push_back(c);
-    }
-    return true;
-}
-
-static const uint8_t BITREV[256] = {
-#define R2(n) n, n + 2 * 64, n + 1 * 64, n + 3 * 64
-#define R4(n) R2(n), R2(n + 2 * 16), R2(n + 1 * 16), R2(n + 3 * 16)
-#define R6(n) R4(n), R4(n + 2 * 4), R4(n + 1 * 4), R4(n + 3 * 4)
-    R6(0), R6(2), R6(1), R6(3)
-#undef R2
-#undef R4
-#undef R6
-};
-
-// ORC PRESENT stream (boolean RLE = byte-RLE over MSB-first bit-packed
-// bytes) -> the parquet-style def-level RleChunks consumed by
-// k_level_scatter (which reads LSB-first: bytes are bit-reversed into the
-// (run,col) levels buffer). Tracks the dense (non-null) cursor.
-static bool prescan_present(const uint8_t *s, int64_t len, int64_t n_rows,
-                            int64_t out_row0, RunCol &rc) {
-    int64_t p = 0, cnt = 0;
-    while (cnt < n_rows) {
-        if (p >= len) {
-            set_error("PRESENT stream overrun");
-            return false;
-        }
-        int8_t h = (int8_t)s[p++];
-        if (h >= 0) {
-            uint8_t v = s[p++];
-            int64_t vals = std::min<int64_t>((int64_t)(h + 3) * 8,
-                                             n_rows - cnt);
-            if (v == 0x00 || v == 0xFF) {
-                RleChunk c{};
-                c.kind = 0;
-                c.value = v ? 1 : 0;
-                c.out_start = out_row0 + cnt;
-                c.count = (int32_t)vals;
-                c.bit_width = 1;
-                c.aux = rc.dense_before;
-                rc.def_host.push_back(c);
-                if (v) rc.dense_before += vals;
-            } else {
-                RleChunk c{};
-                c.kind = 1;
-                c.src = (uint64_t)rc.levels_host.size();
-                c.out_start = out_row0 + cnt;
-                c.count = (int32_t)vals;
-                c.bit_width = 1;
-                c.aux = rc.dense_before;
-                for (int i = 0; i < h + 3; i++)
-                    rc.levels_host.push_back(BITREV[v]);
-                rc.def_host.push_back(c);
-                for (int64_t i = 0; i < vals; i += 8) {
-                    int64_t rem = vals - i;
-                    uint8_t mask = rem >= 8 ? 0xFF : (uint8_t)((1u << rem) - 1);
-                    rc.dense_before += __builtin_popcount(BITREV[v] & mask);
-                }
-            }
-            cnt += vals;
-        } else {
-            int lit = -(int)h;
-            int64_t vals = std::min<int64_t>((int64_t)lit * 8, n_rows - cnt);
-            RleChunk c{};
-            c.kind = 1;
-            c.src = (uint64_t)rc.levels_host.size();
-            c.out_start = out_row0 + cnt;
-            c.count = (int32_t)vals;
-            c.bit_width = 1;
-            c.aux = rc.dense_before;
-            for (int i = 0; i < lit; i++)
-                rc.levels_host.push_back(BITREV[s[p + i]]);
-            rc.def_host.push_back(c);
-            for (int64_t i = 0; i < vals; i++) {
-                uint8_t b = BITREV[s[p + (i >> 3)]];
-                rc.dense_before += (b >> (i & 7)) & 1;
-            }
-            p += lit;
-            cnt += vals;
-        }
-    }
-    return true;
-}
 
 // Message for the ORC decimal bits of a section's device error word
 // (k_orc_varint ORs 1 << (ODC_ERR_SHIFT + ODC_ERR_*)).
@@ -1846,6 +1113,79 @@ static bool check_orc_declared(const std::string &path, const ColSpec &cs,
                   cs.name.c_str(), st.writer_timezone.c_str());
         return false;
     }
+    return true;
+}
+
+// Upload `len` encoded bytes into a plan buffer of len + pad bytes (pad 16:
+// the device bit readers load aligned 16-byte windows) and count them as
+// staged input. nullptr with the error set on failure.
+static void *upload_image(pmh_plan_t *plan, const uint8_t *src, int64_t len,
+                          int pad) {
+    void *dev = plan->bufs.alloc(len + pad);
+    if (!dev) return nullptr;
+    if (len && hipMemcpy(dev, src, len, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("H2D failed");
+        return nullptr;
+    }
+    plan->encoded_bytes_total += len;
+    return dev;
+}
+
+// Upload an ORC side stream whose chunks were prescanned at device base 0
+// and point them at the device copy.
+static bool upload_rebase(pmh_plan_t *plan, const uint8_t *src, int64_t len,
+                          std::vector<Rlev2Chunk> &chunks) {
+    void *dev = upload_image(plan, src, len, 16);
+    if (!dev) return false;
+    for (auto &k : chunks) {
+        k.src += (uint64_t)dev;
+        if (k.kind == 2) k.patch_src += (uint64_t)dev;
+    }
+    return true;
+}
+
+// The bytes of one ORC stream of a column: the file's own, or, in a
+// compressed file, `dec` filled by orc_decompress. `label` names the stream
+// in the error (" PRESENT"; "" for DATA).
+static bool orc_stream_bytes(const FileDesc &fd, const StagedFile &sf,
+                             const ColSpec &cs, const OrcStream *st,
+                             const char *label, std::vector<uint8_t> &dec,
+                             const uint8_t **ptr, int64_t *len) {
+    const OrcFileMeta &om = sf.orc_meta;
+    *ptr = sf.data.data() + st->offset;
+    *len = st->length;
+    if (om.compression == 0) return true;
+    std::string cerr;
+    if (!orc_decompress(*ptr, *len, om.compression, om.compression_block_size,
+                        dec, cerr)) {
+        set_error("%s col %s%s: %s", fd.path.c_str(), cs.name.c_str(), label,
+                  cerr.c_str());
+        return false;
+    }
+    *ptr = dec.data();
+    *len = (int64_t)dec.size();
+    return true;
+}
+
+// Stage a stripe's PRESENT stream into the column's def chunks. The stripe's
+// values then go to the dense buffer: *dense0 = the dense cursor before the
+// stripe, *n_dense = its non-null rows.
+static bool stage_orc_present(const FileDesc &fd, const ColSpec &cs,
+                              const uint8_t *pres, int64_t pres_len,
+                              int64_t n_rows, int64_t row0, RunCol &rc,
+                              int64_t *dense0, int64_t *n_dense,
+                              int *dense_target) {
+    const char *why = "";
+    rc.has_nulls = true;
+    *dense0 = rc.dense_before;
+    if (!prescan_present(pres, pres_len, n_rows, row0, rc.levels_host,
+                         rc.def_host, &rc.dense_before, &why)) {
+        set_error("%s col %s PRESENT: %s", fd.path.c_str(), cs.name.c_str(),
+                  why);
+        return false;
+    }
+    *n_dense = rc.dense_before - *dense0;
+    *dense_target = 1;
     return true;
 }
 
@@ -1964,63 +1304,42 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
             // compressed streams decompress on the host at staging, like
             // the parquet zstd path (on-GPU codecs: §8f); the RLEv2/byte-RLE
             // bytes then upload verbatim
-            const uint8_t *data_ptr = sf.data.data() + data->offset;
-            int64_t data_len = data->length;
-            const uint8_t *pres_ptr =
-                present ? sf.data.data() + present->offset : nullptr;
-            int64_t pres_len = present ? present->length : 0;
+            const uint8_t *data_ptr, *pres_ptr = nullptr;
+            int64_t data_len, pres_len = 0;
             std::vector<uint8_t> data_dec, pres_dec;
-            if (om.compression != 0) {
-                std::string cerr;
-                if (!orc_decompress(data_ptr, data_len, om.compression,
-                                    om.compression_block_size, data_dec,
-                                    cerr)) {
-                    set_error("%s col %s: %s", fd.path.c_str(),
-                              cols[c].name.c_str(), cerr.c_str());
-                    return false;
-                }
-                data_ptr = data_dec.data();
-                data_len = (int64_t)data_dec.size();
-                if (present) {
-                    if (!orc_decompress(pres_ptr, pres_len, om.compression,
-                                        om.compression_block_size, pres_dec,
-                                        cerr)) {
-                        set_error("%s col %s PRESENT: %s", fd.path.c_str(),
-                                  cols[c].name.c_str(), cerr.c_str());
-                        return false;
-                    }
-                    pres_ptr = pres_dec.data();
-                    pres_len = (int64_t)pres_dec.size();
-                }
-            }
+            if (!orc_stream_bytes(fd, sf, cols[c], data, "", data_dec,
+                                  &data_ptr, &data_len) ||
+                (present &&
+                 !orc_stream_bytes(fd, sf, cols[c], present, " PRESENT",
+                                   pres_dec, &pres_ptr, &pres_len)))
+                return false;
+            // where the stripe's values go: its rows of the column, or,
+            // under a PRESENT stream, the dense buffer the level scatter
+            // consumes
+            const int64_t row0 = row_base + stripe_row;
+            int64_t n_dense = st.num_rows;
+            int64_t dense0 = row0;
+            int dense_target = 0;
             if (ckind == ORC_FLOAT || ckind == ORC_DOUBLE) {
                 // FLOAT/DOUBLE DATA streams are raw IEEE754 LE values — the
                 // stream IS the decoded representation, so staging is a copy
                 // (layout, not decode), exactly like parquet PLAIN packing.
-                // With PRESENT, the stream holds only the non-null values
-                // and feeds the dense buffer the level scatter consumes.
-                int64_t row0 = row_base + stripe_row;
+                // With PRESENT, the stream holds only the non-null values.
+                if (present &&
+                    !stage_orc_present(fd, cols[c], pres_ptr, pres_len,
+                                       st.num_rows, row0, rc, &dense0,
+                                       &n_dense, &dense_target))
+                    return false;
+                if (data_len < n_dense * stored) {
+                    set_error("%s col %s: FLOAT/DOUBLE stream short",
+                              fd.path.c_str(), cols[c].name.c_str());
+                    return false;
+                }
                 if (present) {
-                    rc.has_nulls = true;
-                    int64_t before = rc.dense_before;
-                    if (!prescan_present(pres_ptr, pres_len, st.num_rows,
-                                         row0, rc))
-                        return false;
-                    int64_t n_dense = rc.dense_before - before;
-                    if (data_len < n_dense * stored) {
-                        set_error("%s col %s: FLOAT/DOUBLE stream short",
-                                  fd.path.c_str(), cols[c].name.c_str());
-                        return false;
-                    }
                     rc.dense_host.insert(rc.dense_host.end(), data_ptr,
                                          data_ptr + n_dense * stored);
-                    rc.dense_segs.emplace_back(before, n_dense * stored);
+                    rc.dense_segs.emplace_back(dense0, n_dense * stored);
                 } else {
-                    if (data_len < st.num_rows * stored) {
-                        set_error("%s col %s: FLOAT/DOUBLE stream short",
-                                  fd.path.c_str(), cols[c].name.c_str());
-                        return false;
-                    }
                     if (hipMemcpy((uint8_t *)rc.contig + row0 * stored,
                                   data_ptr, st.num_rows * stored,
                                   hipMemcpyHostToDevice) != hipSuccess) {
@@ -2053,38 +1372,22 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                               fd.path.c_str(), cols[c].name.c_str());
                     return false;
                 }
-                const uint8_t *len_ptr = sf.data.data() + lenst->offset;
-                int64_t len_len = lenst->length;
+                const uint8_t *len_ptr;
+                int64_t len_len;
                 std::vector<uint8_t> len_dec;
-                if (om.compression != 0) {
-                    std::string cerr;
-                    if (!orc_decompress(len_ptr, len_len, om.compression,
-                                        om.compression_block_size, len_dec,
-                                        cerr)) {
-                        set_error("%s col %s LENGTH: %s", fd.path.c_str(),
-                                  cols[c].name.c_str(), cerr.c_str());
-                        return false;
-                    }
-                    len_ptr = len_dec.data();
-                    len_len = (int64_t)len_dec.size();
-                }
+                if (!orc_stream_bytes(fd, sf, cols[c], lenst, " LENGTH",
+                                      len_dec, &len_ptr, &len_len))
+                    return false;
                 if (!plan->sdicts[c])
                     plan->sdicts[c].reset(new StrDict());
                 StrDict *sd = plan->sdicts[c].get();
-                int64_t row0 = row_base + stripe_row;
-                int64_t n_dense = st.num_rows;
-                int64_t dense0 = row0;
-                int dense_target = 0;
-                if (present) {
-                    rc.has_nulls = true;
-                    int64_t before = rc.dense_before;
-                    if (!prescan_present(pres_ptr, pres_len, st.num_rows,
-                                         row0, rc))
-                        return false;
-                    n_dense = rc.dense_before - before;
-                    dense0 = before;
-                    dense_target = 1;
-                }
+                if (present &&
+                    !stage_orc_present(fd, cols[c], pres_ptr, pres_len,
+                                       st.num_rows, row0, rc, &dense0,
+                                       &n_dense, &dense_target))
+                    return false;
+                const char *why = "";
+                std::vector<uint64_t> lens;
                 if (cenc == 3) {  // DICTIONARY_V2
                     const OrcStream *dct =
                         orc_find_stream(st, cid, ORC_STREAM_DICTIONARY);
@@ -2093,26 +1396,17 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                                   fd.path.c_str(), cols[c].name.c_str());
                         return false;
                     }
-                    const uint8_t *dp = sf.data.data() + dct->offset;
-                    int64_t dl = dct->length;
+                    const uint8_t *dp;
+                    int64_t dl;
                     std::vector<uint8_t> dict_dec;
-                    if (om.compression != 0) {
-                        std::string cerr;
-                        if (!orc_decompress(dp, dl, om.compression,
-                                            om.compression_block_size,
-                                            dict_dec, cerr)) {
-                            set_error("%s col %s DICTIONARY: %s",
-                                      fd.path.c_str(), cols[c].name.c_str(),
-                                      cerr.c_str());
-                            return false;
-                        }
-                        dp = dict_dec.data();
-                        dl = (int64_t)dict_dec.size();
-                    }
-                    std::vector<uint64_t> lens;
-                    if (!host_rlev2_u(len_ptr, len_len, -1, lens)) {
-                        set_error("%s col %s: LENGTH stream decode failed",
-                                  fd.path.c_str(), cols[c].name.c_str());
+                    if (!orc_stream_bytes(fd, sf, cols[c], dct, " DICTIONARY",
+                                          dict_dec, &dp, &dl))
+                        return false;
+                    if (!host_rlev2(len_ptr, len_len, -1, false, lens,
+                                    &why)) {
+                        set_error("%s col %s: LENGTH stream decode failed "
+                                  "(%s)", fd.path.c_str(),
+                                  cols[c].name.c_str(), why);
                         return false;
                     }
                     std::vector<int32_t> remap(lens.size());
@@ -2135,18 +1429,16 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                         set_error("H2D ORC string remap failed");
                         return false;
                     }
-                    void *dev = plan->bufs.alloc(data_len + 16);
+                    void *dev = upload_image(plan, data_ptr, data_len, 16);
                     if (!dev) return false;
-                    if (hipMemcpy(dev, data_ptr, data_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
-                        return false;
-                    }
-                    plan->encoded_bytes_total += data_len + len_len + dl;
+                    plan->encoded_bytes_total += len_len + dl;
                     if (!prescan_rlev2(data_ptr, data_len, n_dense, 0, 4,
                                        dense_target, (uint64_t)dev, dense0,
-                                       rc.rlev2_host))
+                                       rc.rlev2_host, &why)) {
+                        set_error("%s col %s: %s", fd.path.c_str(),
+                                  cols[c].name.c_str(), why);
                         return false;
+                    }
                     GatherTask gt;
                     gt.start = dense0;
                     gt.n = n_dense;
@@ -2155,10 +1447,11 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                     gt.in_place = true;
                     rc.gathers.push_back(gt);
                 } else {  // DIRECT_V2: host id-ification
-                    std::vector<uint64_t> lens;
-                    if (!host_rlev2_u(len_ptr, len_len, n_dense, lens)) {
-                        set_error("%s col %s: LENGTH stream decode failed",
-                                  fd.path.c_str(), cols[c].name.c_str());
+                    if (!host_rlev2(len_ptr, len_len, n_dense, false, lens,
+                                    &why)) {
+                        set_error("%s col %s: LENGTH stream decode failed "
+                                  "(%s)", fd.path.c_str(),
+                                  cols[c].name.c_str(), why);
                         return false;
                     }
                     std::vector<int32_t> ids(n_dense);
@@ -2192,58 +1485,44 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
             }
             // upload the encoded DATA stream (+16 B pad: the RLEv2
             // bit reader uses an aligned 16-byte window)
-            void *dev = plan->bufs.alloc(data_len + 16);
+            void *dev = upload_image(plan, data_ptr, data_len, 16);
             if (!dev) return false;
-            if (hipMemcpy(dev, data_ptr, data_len, hipMemcpyHostToDevice) !=
-                hipSuccess) {
-                set_error("H2D failed");
+            if (present &&
+                !stage_orc_present(fd, cols[c], pres_ptr, pres_len,
+                                   st.num_rows, row0, rc, &dense0, &n_dense,
+                                   &dense_target))
                 return false;
-            }
-            plan->encoded_bytes_total += data_len;
-            int64_t row0 = row_base + stripe_row;
-            int64_t n_dense = st.num_rows;
-            int64_t dense0 = row0;
-            int dense_target = 0;
-            if (present) {
-                rc.has_nulls = true;
-                int64_t before = rc.dense_before;
-                if (!prescan_present(pres_ptr, pres_len, st.num_rows, row0,
-                                     rc))
+            // DECIMAL and TIMESTAMP: the SECONDARY stream's chunks, based
+            // at 0 until the stream is uploaded
+            const uint8_t *sec_ptr = nullptr;
+            int64_t sec_len = 0;
+            std::vector<uint8_t> sec_dec;
+            std::vector<Rlev2Chunk> sch;
+            const char *why = "";
+            if (secondary) {
+                const bool dec = ckind == ORC_DECIMAL;
+                if (!orc_stream_bytes(fd, sf, cols[c], secondary,
+                                      " SECONDARY", sec_dec, &sec_ptr,
+                                      &sec_len))
                     return false;
-                n_dense = rc.dense_before - before;
-                dense0 = before;
-                dense_target = 1;
+                // decimal: signed data scales to the (run, column) scale
+                // scratch; timestamp: unsigned stored nanos to its nanos
+                // scratch
+                if (!prescan_rlev2(sec_ptr, sec_len, n_dense, dec, dec ? 4 : 8,
+                                   dec ? 2 : 3, 0,
+                                   dec ? rc.scale_rows : rc.nanos_rows, sch,
+                                   &why)) {
+                    set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
+                              cols[c].name.c_str(), why);
+                    return false;
+                }
             }
             bool ok;
             if (ckind == ORC_DECIMAL) {
-                const uint8_t *sec_ptr = sf.data.data() + secondary->offset;
-                int64_t sec_len = secondary->length;
-                std::vector<uint8_t> sec_dec;
-                if (om.compression != 0) {
-                    std::string cerr;
-                    if (!orc_decompress(sec_ptr, sec_len, om.compression,
-                                        om.compression_block_size, sec_dec,
-                                        cerr)) {
-                        set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
-                                  cols[c].name.c_str(), cerr.c_str());
-                        return false;
-                    }
-                    sec_ptr = sec_dec.data();
-                    sec_len = (int64_t)sec_dec.size();
-                }
-                // SECONDARY: signed RLEv2 data scales. Constant runs equal
-                // to the column scale (what the common writers emit) need
-                // no device work at all; anything else decodes through
-                // k_rlev2 into the (run, column) scale scratch
-                std::vector<Rlev2Chunk> sch;
+                // Constant scale runs equal to the column scale (what the
+                // common writers emit) need no device work at all; anything
+                // else decodes through k_rlev2
                 const int64_t sc0 = rc.scale_rows;
-                if (!prescan_rlev2(sec_ptr, sec_len, n_dense, 1, 4, 2, 0,
-                                   sc0, sch)) {
-                    set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
-                              cols[c].name.c_str(),
-                              std::string(last_error()).c_str());
-                    return false;
-                }
                 bool uniform = true;
                 int64_t sc_end = sc0;
                 for (const auto &k : sch) {
@@ -2264,32 +1543,18 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                                   (long long)n_dense);
                         return false;
                     }
-                    void *sdev = plan->bufs.alloc(sec_len + 16);
-                    if (!sdev) return false;
-                    if (hipMemcpy(sdev, sec_ptr, sec_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
+                    if (!upload_rebase(plan, sec_ptr, sec_len, sch))
                         return false;
-                    }
-                    plan->encoded_bytes_total += sec_len;
-                    for (auto &k : sch) {
-                        k.src += (uint64_t)sdev;
-                        if (k.kind == 2) k.patch_src += (uint64_t)sdev;
-                    }
                     rc.rlev2_host.insert(rc.rlev2_host.end(), sch.begin(),
                                          sch.end());
                     rc.scale_rows += n_dense;
                 }
-                const char *why = "";
                 const size_t u0 = rc.varint_host.size();
                 ok = prescan_varint(data_ptr, data_len, n_dense, stored,
                                     cols[c].precision, cols[c].scale,
                                     dense_target, (uint64_t)dev, dense0,
                                     rc.varint_host, &why);
-                if (!ok)
-                    set_error("%s col %s: %s", fd.path.c_str(),
-                              cols[c].name.c_str(), why);
-                else if (!uniform)
+                if (ok && !uniform)
                     for (size_t i = u0; i < rc.varint_host.size(); i++) {
                         VarintUnit &vu = rc.varint_host[i];
                         vu.scale_addr =
@@ -2297,32 +1562,7 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                     }
             } else if (ckind == ORC_TIMESTAMP ||
                        ckind == ORC_TIMESTAMP_INSTANT) {
-                const uint8_t *sec_ptr = sf.data.data() + secondary->offset;
-                int64_t sec_len = secondary->length;
-                std::vector<uint8_t> sec_dec;
-                if (om.compression != 0) {
-                    std::string cerr;
-                    if (!orc_decompress(sec_ptr, sec_len, om.compression,
-                                        om.compression_block_size, sec_dec,
-                                        cerr)) {
-                        set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
-                                  cols[c].name.c_str(), cerr.c_str());
-                        return false;
-                    }
-                    sec_ptr = sec_dec.data();
-                    sec_len = (int64_t)sec_dec.size();
-                }
-                // SECONDARY: unsigned RLEv2 stored nanos, through k_rlev2
-                // into the (run, column) nanos scratch
-                std::vector<Rlev2Chunk> sch;
                 const int64_t n0 = rc.nanos_rows;
-                if (!prescan_rlev2(sec_ptr, sec_len, n_dense, 0, 8, 3, 0, n0,
-                                   sch)) {
-                    set_error("%s col %s SECONDARY: %s", fd.path.c_str(),
-                              cols[c].name.c_str(),
-                              std::string(last_error()).c_str());
-                    return false;
-                }
                 int64_t n_end = n0;
                 for (const auto &k : sch) n_end = k.out_start + k.count;
                 // the scratch is sized by the value count: a stream whose
@@ -2334,25 +1574,13 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
                               (long long)n_dense);
                     return false;
                 }
-                void *sdev = plan->bufs.alloc(sec_len + 16);
-                if (!sdev) return false;
-                if (sec_len && hipMemcpy(sdev, sec_ptr, sec_len,
-                                         hipMemcpyHostToDevice) !=
-                                   hipSuccess) {
-                    set_error("H2D failed");
-                    return false;
-                }
-                plan->encoded_bytes_total += sec_len;
-                for (auto &k : sch) {
-                    k.src += (uint64_t)sdev;
-                    if (k.kind == 2) k.patch_src += (uint64_t)sdev;
-                }
+                if (!upload_rebase(plan, sec_ptr, sec_len, sch)) return false;
                 // DATA: signed RLEv2 seconds relative to 2015-01-01, to the
                 // column (or its dense buffer) as int64
                 const size_t v0 = rc.rlev2_host.size();
                 ok = prescan_rlev2(data_ptr, data_len, n_dense, 1, 8,
                                    dense_target, (uint64_t)dev, dense0,
-                                   rc.rlev2_host);
+                                   rc.rlev2_host, &why);
                 if (ok) {
                     int64_t d_end = dense0;
                     for (size_t i = v0; i < rc.rlev2_host.size(); i++)
@@ -2385,28 +1613,28 @@ static bool stage_orc_file(pmh_plan_t *plan, const FileDesc &fd,
             } else if (ckind == ORC_BOOLEAN) {
                 // DATA: byte-RLE over MSB-first bytes; one unit per run or
                 // literal group, expanded by k_bits_expand at read time
-                const char *why = "";
                 ok = prescan_boolrle(data_ptr, data_len, n_dense, stored,
                                      dense_target, (uint64_t)dev, dense0,
                                      rc.bits_host, &why);
-                if (!ok)
-                    set_error("%s col %s: %s", fd.path.c_str(),
-                              cols[c].name.c_str(), why);
             } else if (ckind == ORC_BYTE) {
                 ok = prescan_byterle(data_ptr, data_len, n_dense, stored,
                                      dense_target, (uint64_t)dev, dense0,
-                                     rc.rlev2_host);
+                                     rc.rlev2_host, &why);
             } else if (ckind == ORC_SHORT || ckind == ORC_INT ||
                        ckind == ORC_LONG || ckind == ORC_DATE) {
                 ok = prescan_rlev2(data_ptr, data_len, n_dense, 1, stored,
                                    dense_target, (uint64_t)dev, dense0,
-                                   rc.rlev2_host);
+                                   rc.rlev2_host, &why);
             } else {
                 set_error("%s col %s: ORC type kind %d not supported yet",
                           fd.path.c_str(), cols[c].name.c_str(), ckind);
                 return false;
             }
-            if (!ok) return false;
+            if (!ok) {
+                set_error("%s col %s: %s", fd.path.c_str(),
+                          cols[c].name.c_str(), why);
+                return false;
+            }
         }
         stripe_row += st.num_rows;
     }
@@ -2457,6 +1685,62 @@ static bool upload_chunk_dict(pmh_plan_t *plan, int c,
         return false;
     }
     *out = dev;
+    return true;
+}
+
+// Byte length of a page's payload in its chunk's uncompressed image.
+static int64_t page_len(const ColumnChunkMeta &cc, const PageMeta &pg) {
+    return cc.codec != CODEC_UNCOMPRESSED ? pg.uncompressed_size
+                                          : pg.compressed_size;
+}
+
+// Upload a chunk's payload image (everything up to its longest page end;
+// ppo = the pages' offsets in it) for the device decoders.
+static void *upload_chunk_image(pmh_plan_t *plan, const ColumnChunkMeta &cc,
+                                const std::vector<int64_t> &ppo,
+                                const uint8_t *payload_base, int pad) {
+    int64_t payload_len = 0;
+    for (size_t pi = 0; pi < cc.pages.size(); pi++)
+        payload_len =
+            std::max(payload_len, ppo[pi] + page_len(cc, cc.pages[pi]));
+    return upload_image(plan, payload_base, payload_len, pad);
+}
+
+// Stage a v1 data page's def levels (pp = the page, vpos = where its values
+// begin: 4 length bytes + the level stream, checked against the page) into
+// the column's levels buffer and def chunks. *before = the dense cursor
+// before the page, *nvalid = the page's non-null values.
+static bool stage_page_def(const FileDesc &fd, const ColSpec &cs,
+                           const uint8_t *pp, int64_t vpos, int64_t n_values,
+                           int64_t out_row0, RunCol &rc, int64_t *before,
+                           int64_t *nvalid) {
+    const int64_t rel = (int64_t)rc.levels_host.size();
+    rc.levels_host.insert(rc.levels_host.end(), pp + 4, pp + vpos);
+    *before = rc.dense_before;
+    const char *why = "";
+    if (!prescan_def(pp + 4, vpos - 4, n_values, out_row0, rel,
+                     &rc.dense_before, rc.def_host, &why)) {
+        set_error("%s col %s: %s", fd.path.c_str(), cs.name.c_str(), why);
+        return false;
+    }
+    *nvalid = rc.dense_before - *before;
+    return true;
+}
+
+// Prescan a dictionary-encoded page's id stream (at vpos of page pp: the bit
+// width byte, then hybrid RLE) into the column's RLE chunks. page_dev = the
+// page's device address.
+static bool stage_page_ids(const FileDesc &fd, const ColSpec &cs,
+                           const uint8_t *pp, int64_t plen, int64_t vpos,
+                           int64_t n_values, int64_t out_base,
+                           uint64_t page_dev, RunCol &rc) {
+    const char *why = "dictionary id stream lacks its bit-width byte";
+    if (vpos >= plen ||
+        !prescan_rle(pp + vpos + 1, plen - vpos - 1, pp[vpos], n_values,
+                     out_base, page_dev, vpos + 1, rc.rle_host, &why)) {
+        set_error("%s col %s: %s", fd.path.c_str(), cs.name.c_str(), why);
+        return false;
+    }
     return true;
 }
 
@@ -2646,9 +1930,15 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                             cend += pg.uncompressed_size;
                         for (auto &pg : cc.pages) {
                             if (pg.page_type == 0) {
-                                uint32_t dl;
-                                memcpy(&dl, file_unc.data() + o, 4);
-                                if (4 + (int64_t)dl > PFX ||
+                                // a length that does not fit the page takes
+                                // the host path, which refuses it
+                                const int64_t have =
+                                    std::min<int64_t>(pg.uncompressed_size,
+                                                      PFX);
+                                uint32_t dl = 0;
+                                if (have >= 4)
+                                    memcpy(&dl, file_unc.data() + o, 4);
+                                if (4 + (int64_t)dl > have ||
                                     def_levels_have_nulls(
                                         file_unc.data() + o + 4, dl,
                                         pg.num_values))
@@ -2821,15 +2111,20 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     auto &pg = cc.pages[pi];
                     if (pg.page_type != 0) continue;
                     const uint8_t *pp = payload_base + ppo[pi];
-                    int64_t pos = 0;
-                    if (max_def > 0) {
-                        uint32_t dl_len;
-                        memcpy(&dl_len, pp, 4);
-                        chunk_nulls |= def_levels_have_nulls(pp + 4, dl_len,
-                                                             pg.num_values);
-                        pos = 4 + dl_len;
+                    if (max_def == 0) continue;
+                    uint32_t dl_len = 0;
+                    if (page_len(cc, pg) >= 4) memcpy(&dl_len, pp, 4);
+                    if (4 + (int64_t)dl_len > page_len(cc, pg)) {
+                        set_error("%s col %s: def-level stream of %lld bytes "
+                                  "does not fit its %lld-byte page",
+                                  fd.path.c_str(), cols[c].name.c_str(),
+                                  (long long)dl_len,
+                                  (long long)page_len(cc, pg));
+                        return false;
                     }
-                    vpos[pi] = pos;
+                    chunk_nulls |= def_levels_have_nulls(pp + 4, dl_len,
+                                                         pg.num_values);
+                    vpos[pi] = 4 + dl_len;
                 }
                 if (cols[c].is_bool) {
                     // PLAIN booleans: 1 bit per value, LSB first, every page
@@ -2838,47 +2133,24 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     // k_bits_expand materialises the column at read time,
                     // into the dense buffer where the chunk has nulls
                     // (k_level_scatter positions them, as for DELTA)
-                    int64_t payload_len = 0;
-                    for (size_t pi = 0; pi < cc.pages.size(); pi++)
-                        payload_len = std::max(
-                            payload_len,
-                            ppo[pi] + (cc.codec != CODEC_UNCOMPRESSED
-                                           ? cc.pages[pi].uncompressed_size
-                                           : cc.pages[pi].compressed_size));
-                    void *dev = plan->bufs.alloc(payload_len + 16);
+                    void *dev =
+                        upload_chunk_image(plan, cc, ppo, payload_base, 16);
                     if (!dev) return false;
-                    if (payload_len &&
-                        hipMemcpy(dev, payload_base, payload_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
-                        return false;
-                    }
-                    plan->encoded_bytes_total += payload_len;
                     if (chunk_nulls) rc.has_nulls = true;
                     for (size_t pi = 0; pi < cc.pages.size(); pi++) {
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
                         const uint8_t *pp = payload_base + ppo[pi];
                         const int64_t pos = vpos[pi];
-                        const int64_t plen = (cc.codec != CODEC_UNCOMPRESSED
-                                                  ? pg.uncompressed_size
-                                                  : pg.compressed_size);
+                        const int64_t plen = page_len(cc, pg);
                         int64_t n_vals = pg.num_values;
                         int64_t out0 = chunk_row0 + pg.first_row;
                         int target = 0;
                         if (chunk_nulls && max_def > 0) {
-                            uint32_t dl_len;
-                            memcpy(&dl_len, pp, 4);
-                            int64_t rel = (int64_t)rc.levels_host.size();
-                            rc.levels_host.insert(rc.levels_host.end(),
-                                                  pp + 4, pp + 4 + dl_len);
-                            int64_t before = rc.dense_before;
-                            if (!prescan_def(pp + 4, dl_len, pg.num_values,
-                                             out0, rel, &rc.dense_before,
-                                             rc.def_host))
+                            if (!stage_page_def(fd, cols[c], pp, pos,
+                                                pg.num_values, out0, rc,
+                                                &out0, &n_vals))
                                 return false;
-                            n_vals = rc.dense_before - before;
-                            out0 = before;
                             target = 1;
                         }
                         const char *why = "";
@@ -2905,60 +2177,46 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
                         const uint8_t *pp = payload_base + ppo[pi];
-                        int64_t plen2 = (cc.codec != CODEC_UNCOMPRESSED
-                                             ? pg.uncompressed_size
-                                             : pg.compressed_size);
+                        int64_t plen2 = page_len(cc, pg);
                         int64_t row0 = chunk_row0 + pg.first_row;
                         int64_t n_dense = pg.num_values;
                         int64_t dense0 = row0;
-                        bool to_dense = false;
-                        if (max_def > 0) {
-                            uint32_t dl_len;
-                            memcpy(&dl_len, pp, 4);
-                            if (chunk_nulls) {
-                                rc.has_nulls = true;
-                                int64_t rel =
-                                    (int64_t)rc.levels_host.size();
-                                rc.levels_host.insert(rc.levels_host.end(),
-                                                      pp + 4,
-                                                      pp + 4 + dl_len);
-                                int64_t before = rc.dense_before;
-                                if (!prescan_def(pp + 4, dl_len,
-                                                 pg.num_values, row0, rel,
-                                                 &rc.dense_before,
-                                                 rc.def_host))
-                                    return false;
-                                n_dense = rc.dense_before - before;
-                                dense0 = before;
-                                to_dense = true;
-                            }
+                        const bool to_dense = max_def > 0 && chunk_nulls;
+                        if (to_dense) {
+                            rc.has_nulls = true;
+                            if (!stage_page_def(fd, cols[c], pp, vpos[pi],
+                                                pg.num_values, row0, rc,
+                                                &dense0, &n_dense))
+                                return false;
                         }
                         int64_t pos = vpos[pi];
                         std::vector<int64_t> pre, suf;
                         const bool dlba =
                             pg.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY;
+                        const char *why = "short of the page's values";
                         int64_t used;
                         if (dlba) {
                             pre.assign((size_t)n_dense, 0);  // no prefixes
                         } else {
-                            used = host_delta_i64(pp + pos, plen2 - pos,
-                                                  pre);
+                            used = host_delta_i64(pp + pos, plen2 - pos, pre,
+                                                  &why);
                             if (used < 0 ||
                                 (int64_t)pre.size() < n_dense) {
                                 set_error("%s col %s: DELTA_BYTE_ARRAY "
-                                          "prefix stream bad",
+                                          "prefix stream bad (%s)",
                                           fd.path.c_str(),
-                                          cols[c].name.c_str());
+                                          cols[c].name.c_str(), why);
                                 return false;
                             }
                             pos += used;
                         }
-                        used = host_delta_i64(pp + pos, plen2 - pos, suf);
+                        used = host_delta_i64(pp + pos, plen2 - pos, suf,
+                                              &why);
                         if (used < 0 ||
                             (int64_t)suf.size() < n_dense) {
                             set_error("%s col %s: DELTA_BYTE_ARRAY suffix "
-                                      "stream bad", fd.path.c_str(),
-                                      cols[c].name.c_str());
+                                      "stream bad (%s)", fd.path.c_str(),
+                                      cols[c].name.c_str(), why);
                             return false;
                         }
                         pos += used;
@@ -3007,69 +2265,38 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     // upload the encoded payload image (+16 B pad for the
                     // device bit-window loads); blocks decode on GPU at
                     // read time (k_delta_sum/scan/emit)
-                    int64_t payload_len = 0;
-                    for (size_t pi = 0; pi < cc.pages.size(); pi++)
-                        payload_len = std::max(
-                            payload_len,
-                            ppo[pi] + (cc.codec != CODEC_UNCOMPRESSED
-                                           ? cc.pages[pi].uncompressed_size
-                                           : cc.pages[pi].compressed_size));
-                    void *dev = plan->bufs.alloc(payload_len + 16);
+                    void *dev =
+                        upload_chunk_image(plan, cc, ppo, payload_base, 16);
                     if (!dev) return false;
-                    if (hipMemcpy(dev, payload_base, payload_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
-                        return false;
-                    }
-                    plan->encoded_bytes_total += payload_len;
                     if (chunk_nulls) rc.has_nulls = true;
                     for (size_t pi = 0; pi < cc.pages.size(); pi++) {
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
                         const uint8_t *pp = payload_base + ppo[pi];
                         int64_t pos = vpos[pi];
-                        int64_t plen = (cc.codec != CODEC_UNCOMPRESSED
-                                            ? pg.uncompressed_size
-                                            : pg.compressed_size);
-                        std::string derr;
+                        int64_t n_vals = pg.num_values;
+                        int64_t out0 = chunk_row0 + pg.first_row;
+                        uint64_t out_addr = (uint64_t)rc.contig;
                         if (chunk_nulls && max_def > 0) {
                             // nullable DELTA: the stream encodes only the
                             // NON-NULL values — decode them to the dense
                             // buffer (out_addr 0 patched to dense_dev at
                             // finalize) and let k_level_scatter position
                             // them like dense PLAIN/dictionary values
-                            uint32_t dl_len;
-                            memcpy(&dl_len, pp, 4);
-                            int64_t rel = (int64_t)rc.levels_host.size();
-                            rc.levels_host.insert(rc.levels_host.end(),
-                                                  pp + 4, pp + 4 + dl_len);
-                            int64_t before = rc.dense_before;
-                            if (!prescan_def(pp + 4, dl_len, pg.num_values,
-                                             chunk_row0 + pg.first_row, rel,
-                                             &rc.dense_before, rc.def_host))
+                            if (!stage_page_def(fd, cols[c], pp, pos,
+                                                pg.num_values, out0, rc,
+                                                &out0, &n_vals))
                                 return false;
-                            int64_t nvalid = rc.dense_before - before;
-                            if (!prescan_delta(pp + pos, plen - pos, nvalid,
-                                               before, (uint64_t)dev,
-                                               ppo[pi] + pos, 0ull, stored,
-                                               rc.delta_host,
-                                               rc.dstreams_host, derr)) {
-                                set_error("%s col %s: %s", fd.path.c_str(),
-                                          cols[c].name.c_str(),
-                                          derr.c_str());
-                                return false;
-                            }
-                            continue;
+                            out_addr = 0;
                         }
-                        if (!prescan_delta(pp + pos, plen - pos,
-                                           pg.num_values,
-                                           chunk_row0 + pg.first_row,
-                                           (uint64_t)dev, ppo[pi] + pos,
-                                           (uint64_t)rc.contig, stored,
+                        const char *why = "";
+                        if (!prescan_delta(pp + pos, page_len(cc, pg) - pos,
+                                           n_vals, out0, (uint64_t)dev,
+                                           ppo[pi] + pos, out_addr, stored,
                                            rc.delta_host, rc.dstreams_host,
-                                           derr)) {
+                                           &why)) {
                             set_error("%s col %s: %s", fd.path.c_str(),
-                                      cols[c].name.c_str(), derr.c_str());
+                                      cols[c].name.c_str(), why);
                             return false;
                         }
                     }
@@ -3085,45 +2312,22 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                         return false;
                     }
                     rc.dict_encoded = true;
-                    int64_t payload_len = 0;
-                    for (size_t pi = 0; pi < cc.pages.size(); pi++)
-                        payload_len = std::max(
-                            payload_len,
-                            ppo[pi] + (cc.codec != CODEC_UNCOMPRESSED
-                                           ? cc.pages[pi].uncompressed_size
-                                           : cc.pages[pi].compressed_size));
-                    void *dev = plan->bufs.alloc(payload_len);
+                    void *dev =
+                        upload_chunk_image(plan, cc, ppo, payload_base, 0);
                     if (!dev) return false;
-                    if (hipMemcpy(dev, payload_base, payload_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
-                        return false;
-                    }
-                    plan->encoded_bytes_total += payload_len;
                     int64_t dense_start = rc.dense_before;
                     for (size_t pi = 0; pi < cc.pages.size(); pi++) {
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
                         const uint8_t *pp = payload_base + ppo[pi];
-                        uint32_t dl_len;
-                        memcpy(&dl_len, pp, 4);
-                        int64_t rel = (int64_t)rc.levels_host.size();
-                        rc.levels_host.insert(rc.levels_host.end(), pp + 4,
-                                              pp + 4 + dl_len);
-                        int64_t before = rc.dense_before;
-                        if (!prescan_def(pp + 4, dl_len, pg.num_values,
-                                         chunk_row0 + pg.first_row, rel,
-                                         &rc.dense_before, rc.def_host))
-                            return false;
-                        int64_t nvalid = rc.dense_before - before;
-                        int64_t pos = vpos[pi];
-                        int bw = pp[pos];
-                        int64_t plen = (cc.codec != CODEC_UNCOMPRESSED
-                                            ? pg.uncompressed_size
-                                            : pg.compressed_size);
-                        if (!prescan_rle(pp + pos + 1, plen - pos - 1, bw,
-                                         nvalid, before, (uint64_t)dev,
-                                         ppo[pi] + pos + 1, rc.rle_host))
+                        int64_t before, nvalid;
+                        if (!stage_page_def(fd, cols[c], pp, vpos[pi],
+                                            pg.num_values,
+                                            chunk_row0 + pg.first_row, rc,
+                                            &before, &nvalid) ||
+                            !stage_page_ids(fd, cols[c], pp, page_len(cc, pg),
+                                            vpos[pi], nvalid, before,
+                                            (uint64_t)dev + ppo[pi], rc))
                             return false;
                     }
                     void *dict_dev = nullptr;
@@ -3144,17 +2348,12 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
                         const uint8_t *pp = payload_base + ppo[pi];
-                        uint32_t dl_len;
-                        memcpy(&dl_len, pp, 4);
-                        int64_t rel = (int64_t)rc.levels_host.size();
-                        rc.levels_host.insert(rc.levels_host.end(), pp + 4,
-                                              pp + 4 + dl_len);
-                        int64_t before = rc.dense_before;
-                        if (!prescan_def(pp + 4, dl_len, pg.num_values,
-                                         chunk_row0 + pg.first_row, rel,
-                                         &rc.dense_before, rc.def_host))
+                        int64_t before, nvalid;
+                        if (!stage_page_def(fd, cols[c], pp, vpos[pi],
+                                            pg.num_values,
+                                            chunk_row0 + pg.first_row, rc,
+                                            &before, &nvalid))
                             return false;
-                        int64_t nvalid = rc.dense_before - before;
                         rc.dense_host.insert(
                             rc.dense_host.end(), pp + vpos[pi],
                             pp + vpos[pi] + nvalid * stored);
@@ -3212,35 +2411,18 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                     }
                     rc.dict_encoded = true;
                     // upload the id-stream payload image
-                    int64_t payload_len = 0;
-                    for (size_t pi = 0; pi < cc.pages.size(); pi++)
-                        payload_len =
-                            std::max(payload_len,
-                                     ppo[pi] + (cc.codec != CODEC_UNCOMPRESSED
-                                                    ? cc.pages[pi].uncompressed_size
-                                                    : cc.pages[pi].compressed_size));
-                    void *dev = plan->bufs.alloc(payload_len);
+                    void *dev =
+                        upload_chunk_image(plan, cc, ppo, payload_base, 0);
                     if (!dev) return false;
-                    if (hipMemcpy(dev, payload_base, payload_len,
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        set_error("H2D failed");
-                        return false;
-                    }
-                    plan->encoded_bytes_total += payload_len;
                     for (size_t pi = 0; pi < cc.pages.size(); pi++) {
                         auto &pg = cc.pages[pi];
                         if (pg.page_type != 0) continue;
-                        const uint8_t *pp = payload_base + ppo[pi];
-                        int64_t pos = vpos[pi];
-                        int bw = pp[pos];
-                        int64_t plen = (cc.codec != CODEC_UNCOMPRESSED
-                                            ? pg.uncompressed_size
-                                            : pg.compressed_size);
-                        if (!prescan_rle(pp + pos + 1, plen - pos - 1, bw,
-                                         pg.num_values,
-                                         chunk_row0 + pg.first_row,
-                                         (uint64_t)dev, ppo[pi] + pos + 1,
-                                         rc.rle_host))
+                        if (!stage_page_ids(fd, cols[c],
+                                            payload_base + ppo[pi],
+                                            page_len(cc, pg), vpos[pi],
+                                            pg.num_values,
+                                            chunk_row0 + pg.first_row,
+                                            (uint64_t)dev + ppo[pi], rc))
                             return false;
                     }
                     void *dict_dev = nullptr;
@@ -5323,8 +4505,10 @@ int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
             return -1;
         }
         std::vector<uint64_t> v;
-        if (!host_rlev2_u(s, len, n_values, v)) {
-            set_error("pmh_debug_orc_ints: host RLEv2 decode failed");
+        const char *why = "";
+        if (!host_rlev2(s, len, n_values, false, v, &why)) {
+            set_error("pmh_debug_orc_ints: host RLEv2 decode failed (%s)",
+                      why);
             return -1;
         }
         int64_t n = std::min<int64_t>((int64_t)v.size(), out_cap);
@@ -5338,10 +4522,14 @@ int64_t pmh_debug_orc_ints(const void *stream, int64_t len, int64_t n_values,
         return -1;
     }
     auto prescan = [&](uint64_t dev_base, std::vector<Rlev2Chunk> &ch) {
-        return kind == 2 ? prescan_byterle(s, len, n_values, out_esize, 0,
-                                           dev_base, 0, ch)
-                         : prescan_rlev2(s, len, n_values, kind == 0,
-                                         out_esize, 0, dev_base, 0, ch);
+        const char *why = "";
+        const bool ok =
+            kind == 2 ? prescan_byterle(s, len, n_values, out_esize, 0,
+                                        dev_base, 0, ch, &why)
+                      : prescan_rlev2(s, len, n_values, kind == 0, out_esize,
+                                      0, dev_base, 0, ch, &why);
+        if (!ok) set_error("%s", why);
+        return ok;
     };
     std::vector<Rlev2Chunk> chunks;
     if (mode == 1) {  // prescan only: dummy device base
@@ -5699,11 +4887,12 @@ int64_t pmh_debug_orc_timestamp(const void *data, int64_t data_len,
     auto prescan = [&](uint64_t d_base, uint64_t s_base) {
         dch.clear();
         sch.clear();
-        if (!prescan_rlev2(ds, data_len, n_values, 1, 8, 0, d_base, 0, dch) ||
+        const char *why = "";
+        if (!prescan_rlev2(ds, data_len, n_values, 1, 8, 0, d_base, 0, dch,
+                           &why) ||
             !prescan_rlev2(ss, secondary_len, n_values, 0, 8, 3, s_base, 0,
-                           sch)) {
-            const std::string why = last_error();
-            set_error("pmh_debug_orc_timestamp: %s", why.c_str());
+                           sch, &why)) {
+            set_error("pmh_debug_orc_timestamp: %s", why);
             return false;
         }
         int64_t d_end = 0, s_end = 0;
@@ -5720,8 +4909,9 @@ int64_t pmh_debug_orc_timestamp(const void *data, int64_t data_len,
     if (mode == 0) {  // host: the oracle-independent host RLEv2 + the core
         if (!prescan(0x1000, 0x1000)) return -1;
         std::vector<uint64_t> secs_zz, nanos;
-        if (!host_rlev2_s(ds, data_len, n_values, secs_zz) ||
-            !host_rlev2_u(ss, secondary_len, n_values, nanos) ||
+        const char *why = "";
+        if (!host_rlev2(ds, data_len, n_values, true, secs_zz, &why) ||
+            !host_rlev2(ss, secondary_len, n_values, false, nanos, &why) ||
             (int64_t)secs_zz.size() < n_values ||
             (int64_t)nanos.size() < n_values) {
             set_error("pmh_debug_orc_timestamp: host RLEv2 decode failed");
