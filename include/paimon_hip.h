@@ -201,7 +201,16 @@ int pmh_plan_close(pmh_plan_t *p);
  * "full-compaction" in the plan JSON, with "max_level" and optional
  * "changelog_row_deduplicate"): the FullChangelogMergeFunctionWrapper
  * stream (INSERT / UPDATE_BEFORE / UPDATE_AFTER / DELETE rows in key
- * order, same schema as the main batch). changelog_producer = "lookup"
+ * order, same schema as the main batch) for every merge engine. With
+ * partial-update and aggregation an UPDATE_BEFORE / DELETE row carries the
+ * max-level record's own key, sequence number and values, an INSERT /
+ * UPDATE_AFTER row the folded row exactly as the main batch holds it (key,
+ * last member's sequence number, values, validity); rows do not depend on
+ * drop_delete; row-deduplicate compares the max-level record with the
+ * folded row, validity first, then the stored bits. Those two engines
+ * refuse ignore_delete with this producer, and a section whose runs x
+ * columns exceed the changelog kernels' 48 KB column table (16 bytes per
+ * run and column). changelog_producer = "lookup"
  * serves the LookupChangelogMergeFunctionWrapper stream the same way; a row
  * built from a looked-up record carries that record's key, sequence number
  * and values. Valid until the next read_next. Returns row count or < 0. */
@@ -393,6 +402,26 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
                            const int64_t *level_rows, const int64_t *queries,
                            int64_t n_queries, int32_t *out_level,
                            int64_t *out_row);
+
+/* The full-compaction changelog decision table on the host, through the same
+ * core the partial-update / aggregation walk of k_merge_tiles runs on the
+ * device (changelog_core.h, FullChangelogMergeFunctionWrapper.java:96-126).
+ * Per key group g: nlive[g] >= 1 live records, n_top[g] of them from a
+ * max-level run (0 <= n_top <= nlive), merged_is_add[g] != 0 when the
+ * wrapper's result is an add (the lone record itself when nlive == 1).
+ * pending != 0 = changelog-producer.row-deduplicate is on. Writes out_n[g] =
+ * 0, 1 or 2 changelog rows and their RowKinds to out_kinds[2g], [2g + 1]
+ * (0 INSERT, 1 UPDATE_BEFORE, 2 UPDATE_AFTER, 3 DELETE; -1 = no row).
+ * Optional (may be NULL): out_after_is_merged[g] = the last row carries the
+ * merged result (otherwise every row carries the top-level record);
+ * out_pending[g] = the pair still awaits the value-equality check that may
+ * drop it. Returns 0, or -1 with pmh_last_error() set. */
+int pmh_debug_changelog_decide(int64_t n_groups, const int32_t *nlive,
+                               const int32_t *n_top,
+                               const uint8_t *merged_is_add, int pending,
+                               int32_t *out_n, int8_t *out_kinds,
+                               uint8_t *out_after_is_merged,
+                               uint8_t *out_pending);
 
 /* The merge-path partition on its own: k runs of ascending unique keys
  * (keys[r] holds lens[r] elements of key_width 4 = int32 or 8 = int64; an

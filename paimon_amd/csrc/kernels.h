@@ -112,6 +112,35 @@ hipError_t pmh_launch_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
                               int64_t tile_rows, void *const *out_ptrs,
                               uint8_t *const *out_valid, hipStream_t stream);
 
+// The same chain for the folding engines (partial-update / aggregation),
+// whose after-type rows are the engine's folded result: merge flags bit
+// PMH_FLAG_FOLD_CL selects the changelog walk of the PU k_merge_tiles, whose
+// after-type entries name the main-output row tile_offsets[tile] + g
+// (changelog_core.h). Both kernels therefore run after the engine's emit
+// kernel on the same stream and read out_ptrs / out_valid (the plan's main
+// output); emit writes out_ptrs2 / out_valid2. They stage pmh_fold_cl_lds(k,
+// n_cols) bytes of per-run column tables in LDS and need contiguous columns
+// (n_pages == 1); the launchers return hipErrorInvalidValue past
+// PMH_FOLD_CL_LDS_MAX (plan creation refuses such a section first).
+constexpr int PMH_FLAG_FOLD_CL = 1 << 16;
+constexpr int64_t PMH_FOLD_CL_LDS_MAX = 48 * 1024;
+constexpr int64_t pmh_fold_cl_lds(int64_t k, int64_t n_cols) {
+    return 16 * k * n_cols + 32 * n_cols + ((n_cols + 7) & ~(int64_t)7);
+}
+hipError_t pmh_launch_cl_finalize_out(
+    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
+    int n_cols, int first_val, int k, const uint64_t *cl_entries,
+    uint64_t *cl_out, int32_t *cl_counts, const int64_t *tile_offsets,
+    int64_t n_tiles, int64_t tile_rows, void *const *out_ptrs,
+    uint8_t *const *out_valid, hipStream_t stream);
+hipError_t pmh_launch_cl_emit_out(
+    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
+    int n_cols, int k, int kind_col, const uint64_t *cl_rows,
+    const int32_t *cl_counts, const int64_t *cl_offsets,
+    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
+    void *const *out_ptrs, uint8_t *const *out_valid, void *const *out_ptrs2,
+    uint8_t *const *out_valid2, hipStream_t stream);
+
 // on-GPU zstd page decompression (k_zstd_pages): one job per parquet page.
 // scratch must hold n_jobs * PZ_SLOT bytes (PZ_SLOT in zstd_core.h);
 // status[j] = decompressed bytes or a PZ_ERR_* code.

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "changelog_core.h"
 #include "kernels.h"
 #include "lookup_core.h"
 #include "partition_core.h"
@@ -358,8 +359,12 @@ DEV T gload(uint64_t addr) {
 // tile's merge) before the registers go to LDS. The tile's segment setup goes
 // to `st`; the caller's next barrier publishes it. [S0, S0 + NS) is the slot
 // range: a caller short of registers stages a tile in two halves (the
-// first call writes the setup).
-template <int KM, bool TOMBS, int HS, int S0 = 0, int NS = PMH_TILE_ITER>
+// first call writes the setup). TAG only names a separate copy: a kernel
+// instantiation added later passes its own, so the copies the existing
+// kernels inline keep the callers they had (the inliner treats a copy with
+// one caller differently, and their code would change with it).
+template <int KM, bool TOMBS, int HS, int S0 = 0, int NS = PMH_TILE_ITER,
+          int TAG = 0>
 DEV void tile_prefetch(const TileSmem &sm, TileSetup &st,
                        const int32_t *__restrict__ cuts,
                        const int64_t *__restrict__ lens, int64_t tile, int k,
@@ -495,7 +500,14 @@ DEV void tile_prefetch(const TileSmem &sm, TileSetup &st,
 // applies LookupMergeFunction's level rules and reads k_lookup_probe's
 // per-row probe words; its own instantiation, so the other modes' code is
 // untouched.
-template <bool PU, bool FR, bool LK, int KM, bool TOMBS>
+//
+// PCL=true (with PU): full-compaction changelog for the folding engines
+// (partial-update / aggregation; flags bit PMH_FLAG_FOLD_CL). The member-list
+// walk also writes provisional changelog entries: a before-type row names
+// the group's top-level member, an after-type row the engine's folded result
+// by the group's tile-local index among the kept groups (changelog_core.h).
+// Its own instantiation again.
+template <bool PU, bool FR, bool LK, int KM, bool TOMBS, bool PCL = false>
 __attribute__((amdgpu_waves_per_eu(4))) __launch_bounds__(PMH_TILE_THREADS, 2)
 __global__
 void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
@@ -568,8 +580,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
     for (int64_t tile = blockIdx.x; tile < n_tiles;
          tile += gridDim.x, cb ^= 1) {
         if (!PIPE)
-            tile_prefetch<KM, TOMBS, 2, 0, HALF>(sm, sm.setup[cb], cuts, lens,
-                                                 tile, k, kes, tid, rg);
+            tile_prefetch<KM, TOMBS, 2, 0, HALF, PCL>(
+                sm, sm.setup[cb], cuts, lens, tile, k, kes, tid, rg);
         // publishes setup[cb] and ends the previous tile's LDS reads
         __syncthreads();
         const TileSetup &st = sm.setup[cb];
@@ -601,9 +613,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             store_slots(0, PMH_TILE_ITER);
         } else {
             store_slots(0, HALF);
-            tile_prefetch<KM, TOMBS, 2, HALF, HALF>(sm, sm.setup[cb], cuts,
-                                                    lens, tile, k, kes, tid,
-                                                    rg);
+            tile_prefetch<KM, TOMBS, 2, HALF, HALF, PCL>(
+                sm, sm.setup[cb], cuts, lens, tile, k, kes, tid, rg);
             store_slots(HALF, HALF);
         }
         if (tid < 64) {
@@ -753,8 +764,14 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             uint16_t *gout = &group_start[tile * (tile_rows + 1)];
             bool bad_kind = false;
             int32_t g_off = 0, m_off = 0, total_g = 0, total_m = 0;
+            // PCL: slot of this thread's first changelog entry pair
+            [[maybe_unused]] int32_t c_off = 0;
+            [[maybe_unused]] uint64_t *clout = nullptr;
+            if constexpr (PCL)
+                clout = &cl_entries[tile * 2 * (tile_rows + PMH_MAX_RUNS)];
             for (int pass = 0; pass < 2; pass++) {
                 int32_t ng = 0, nm = 0;
+                [[maybe_unused]] int32_t ncl = 0;
                 for (int32_t i = my_lo; i < my_hi; i++) {
                     if (!sm.head[i]) continue;
                     // pre-scan the group: LIVE members only (deletion-
@@ -765,6 +782,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     int64_t mx = INT64_MIN;
                     bool any_add = false;
                     uint16_t live1 = 0;
+                    [[maybe_unused]] uint16_t s_top = 0;
+                    [[maybe_unused]] int n_top = 0;
                     for (int32_t x = i;; x++) {
                         int64_t v = sm.sseq[mo[x]];
                         if (v != PMH_DEAD) {
@@ -772,6 +791,12 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                             nlive++;
                             if (v > mx) mx = v;
                             any_add |= ps2m_isadd(v);
+                            if constexpr (PCL) {
+                                if (run_levels[run_of(mo[x])] == max_level) {
+                                    s_top = mo[x];
+                                    n_top++;
+                                }
+                            }
                         }
                         if (!(x + 1 < M && !sm.head[x + 1])) {
                             tail = x;
@@ -779,6 +804,50 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                         }
                     }
                     if (nlive == 0) continue;
+                    if constexpr (PCL) {
+                        // changelog decision of every live group, before a
+                        // dropped result leaves the walk: entries do not
+                        // depend on drop-delete. merged = the wrapper's
+                        // result; its kind follows the drop rules below.
+                        if (n_top > 1 && err_flag)
+                            atomicOr(err_flag, 8u);  // checkState :76-78
+                        const bool m_add =
+                            nlive == 1 ? ps2m_isadd(sm.sseq[live1])
+                            : seqg     ? any_add
+                            : rrod     ? ps2m_isadd(mx)
+                                       : true;
+                        const ClcDecision d = clc_decide(
+                            nlive, n_top, m_add, (flags & 128) != 0);
+                        if (d.n) {
+                            if (pass == 1) {
+                                const uint64_t pd =
+                                    CLC_VALID | (d.pending ? CLC_PENDING : 0);
+                                // a group with an after-type row is kept
+                                // (merged is an add): g_off + ng is its
+                                // tile-local index in the main output
+                                const uint64_t after =
+                                    (uint64_t)(uint32_t)(g_off + ng) |
+                                    CLC_FROM_OUT | pd;
+                                const int tr = run_of(s_top);
+                                const uint64_t before =
+                                    ((uint32_t)tr << PMH_ROW_BITS) |
+                                    (uint32_t)((int32_t)s_top +
+                                               st.rowoff[tr]) |
+                                    pd;
+                                const uint64_t k0 = (uint64_t)d.kind0
+                                                    << CLC_KIND_SHIFT;
+                                const uint64_t k1 = (uint64_t)d.kind1
+                                                    << CLC_KIND_SHIFT;
+                                clout[2 * (c_off + ncl)] =
+                                    (d.n == 2 || !d.after_is_merged ? before
+                                                                    : after) |
+                                    k0;
+                                clout[2 * (c_off + ncl) + 1] =
+                                    d.n == 2 ? after | k1 : 0;
+                            }
+                            ncl++;
+                        }
+                    }
                     if (nlive == 1) {
                         // ReducerMergeFunctionWrapper singleton bypass
                         // (ReducerMergeFunctionWrapper.java:53-73): the lone
@@ -835,8 +904,12 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     nm += nlive;
                 }
                 if (pass == 0) {
-                    // dual wave scan of (ng, nm)
+                    // dual wave scan of (ng, nm). PCL: the changelog pair
+                    // count rides in the high half of the group word — a
+                    // tile holds at most PMH_TILE_MAX < 2^16 groups, so
+                    // neither half carries into the other
                     int32_t ig = ng, im = nm;
+                    if constexpr (PCL) ig |= ncl << 16;
                     for (int off = 1; off < 64; off <<= 1) {
                         int32_t ug = __shfl_up(ig, off, 64);
                         int32_t um = __shfl_up(im, off, 64);
@@ -861,6 +934,13 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                         }
                         total_g += sm.wave_tot[w];
                         total_m += sm.wave_tot[NW + w];
+                    }
+                    if constexpr (PCL) {
+                        c_off = ((addg + ig) >> 16) - ncl;
+                        addg &= 0xffff;
+                        ig &= 0xffff;
+                        if (tid == 0) cl_counts[tile] = total_g >> 16;
+                        total_g &= 0xffff;
                     }
                     g_off = addg + ig - ng;
                     m_off = addm + im - nm;
@@ -4191,6 +4271,262 @@ __global__ void k_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
     }
 }
 
+// ------------------------------------- k_cl_finalize_out / k_cl_emit_out
+//
+// The changelog chain of the folding engines (partial-update / aggregation).
+// An after-type row there is the engine's folded result, which is no (run,
+// row) of any input: its entry carries CLC_FROM_OUT and the group's tile-local
+// index g among the kept groups, and the row is read from the plan's MAIN
+// output at tile_offsets[tile] + g — where k_emit_pu / k_emit_pu_sg /
+// k_emit_agg wrote it, so both kernels run after the engine's emit on the
+// same stream. Before-type rows name the top-level record as (run, row), as
+// in k_cl_finalize / k_cl_emit.
+//
+// Both kernels keep one workgroup per tile (grid-stride) and read nothing
+// but entries and column data inside their loops: per run and column the
+// source address / validity address, per column the main and changelog
+// output pointers and the output width, are staged in LDS once per block
+// (pmh_fold_cl_lds bytes; plan creation refuses a section whose tables exceed
+// PMH_FOLD_CL_LDS_MAX or whose columns are paged). Data moves through
+// address_space(1) pointers.
+constexpr int FOLD_CL_THREADS = 256;
+constexpr int FOLD_CL_G = 4;  // columns whose loads are in flight together
+
+struct FoldClTables {
+    uint64_t *addr;    // [k * n_cols] source element 0
+    uint64_t *valid;   // [k * n_cols] source validity bytes, 0 = all valid
+    uint64_t *out;     // [n_cols] main output column
+    uint64_t *ov;      // [n_cols] main output validity, 0 = none
+    uint64_t *out2;    // [n_cols] changelog output column
+    uint64_t *ov2;     // [n_cols] changelog output validity, 0 = none
+    uint8_t *width;    // [n_cols] output width 1 / 2 / 4 / 8; 0 = not moved
+};
+
+// Carve the tables out of dynamic LDS and fill them; ends with a barrier
+// that every thread of the block reaches.
+DEV FoldClTables fold_cl_stage(uint64_t *smem, const DevCol *cols,
+                               const uint8_t *col_dtype,
+                               const uint8_t *col_nullable, int n_cols, int k,
+                               void *const *out_ptrs,
+                               uint8_t *const *out_valid,
+                               void *const *out_ptrs2,
+                               uint8_t *const *out_valid2) {
+    FoldClTables t;
+    const int n_ent = k * n_cols;
+    t.addr = smem;
+    t.valid = t.addr + n_ent;
+    t.out = t.valid + n_ent;
+    t.ov = t.out + n_cols;
+    t.out2 = t.ov + n_cols;
+    t.ov2 = t.out2 + n_cols;
+    t.width = (uint8_t *)(t.ov2 + n_cols);
+    for (int e = threadIdx.x; e < n_ent; e += FOLD_CL_THREADS) {
+        t.addr[e] = cols[e].addr0;
+        t.valid[e] = cols[e].valid0;
+    }
+    for (int c = threadIdx.x; c < n_cols; c += FOLD_CL_THREADS) {
+        const int dt = col_dtype[c];
+        t.width[c] = dt == 1 ? 1
+                     : dt == 2 ? 2
+                     : (dt == 3 || dt == 5 || dt == 7) ? 4
+                     : (dt == 4 || dt == 6) ? 8
+                                            : 0;
+        t.out[c] = (uint64_t)out_ptrs[c];
+        t.ov[c] = col_nullable[c] ? (uint64_t)out_valid[c] : 0;
+        t.out2[c] = out_ptrs2 ? (uint64_t)out_ptrs2[c] : 0;
+        t.ov2[c] =
+            out_valid2 && col_nullable[c] ? (uint64_t)out_valid2[c] : 0;
+    }
+    __syncthreads();
+    return t;
+}
+
+// Value of column c (output width w) as the OUTPUT stores it, sign-extended
+// to 64 bits. src: the source row `row` of run-table base `rb` (stored width
+// 4 for w <= 4, else 8), narrowed the way the emit kernels narrow; else row
+// `row` of the main output.
+DEV int64_t fold_cl_value(const FoldClTables &t, int c, int w, bool src,
+                          int rb, uint64_t row) {
+    const uint64_t base = src ? t.addr[rb + c] : t.out[c];
+    if (w == 8) return gload<int64_t>(base + row * 8);
+    if (w == 4 || src) {
+        const int32_t v = gload<int32_t>(base + row * 4);
+        return w == 1 ? (int64_t)(int8_t)v : w == 2 ? (int64_t)(int16_t)v : v;
+    }
+    return w == 2 ? (int64_t)gload<int16_t>(base + row * 2)
+                  : (int64_t)gload<int8_t>(base + row);
+}
+
+DEV uint8_t fold_cl_validity(const FoldClTables &t, int c, bool src, int rb,
+                             uint64_t row) {
+    const uint64_t va = src ? t.valid[rb + c] : t.ov[c];
+    return va ? gload<uint8_t>(va + row) : (uint8_t)1;
+}
+
+// Compact the provisional entries of the folded walk into dense per-tile
+// rows, as k_cl_finalize does. A pending UPDATE_BEFORE / UPDATE_AFTER pair
+// compares top's source row with the main-output row of its group, value
+// columns only: validity first, then the bits the output stores (both sides
+// null = equal whatever the bits). cl_counts[tile] goes from pair count to
+// row count. A thread owns a contiguous range of <= 16 pairs (2-bit verdicts
+// in one register), so rows stay in key order; the block scan is k_scan_tiles'
+// (wave shuffles + one barrier per tile, wave totals double-buffered).
+__launch_bounds__(FOLD_CL_THREADS) __global__
+void k_cl_finalize_out(const DevCol *cols, const uint8_t *col_dtype,
+                       const uint8_t *col_nullable, int n_cols, int first_val,
+                       int k, const uint64_t *cl_entries, uint64_t *cl_out,
+                       int32_t *cl_counts, const int64_t *tile_offsets,
+                       int64_t n_tiles, int64_t tile_rows,
+                       void *const *out_ptrs, uint8_t *const *out_valid) {
+    extern __shared__ uint64_t fold_smem[];
+    constexpr int NW = FOLD_CL_THREADS / 64;
+    __shared__ int32_t wave_tot[2][NW];
+    const FoldClTables t =
+        fold_cl_stage(fold_smem, cols, col_dtype, col_nullable, n_cols, k,
+                      out_ptrs, out_valid, nullptr, nullptr);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int64_t cap = tile_rows + PMH_MAX_RUNS;  // pairs a tile can hold
+    int buf = 0;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;
+         tile += gridDim.x, buf ^= 1) {
+        const uint64_t *in = &cl_entries[tile * 2 * cap];
+        uint64_t *out = &cl_out[tile * 2 * cap];
+        int32_t ng = cl_counts[tile];
+        ng = ng < 0 ? 0 : (ng > cap ? (int32_t)cap : ng);
+        const int64_t ob = tile_offsets[tile];
+        const int32_t per = (ng + FOLD_CL_THREADS - 1) / FOLD_CL_THREADS;
+        const int32_t lo = tid * per;
+        const int32_t hi = lo + per < ng ? lo + per : ng;
+        uint32_t verd = 0;  // 2 bits per pair: rows that survive
+        int32_t nrows = 0;
+        for (int32_t g = lo; g < hi; g++) {
+            const uint64_t e0 = in[2 * g], e1 = in[2 * g + 1];
+            int nv = (int)((e0 >> 35) & 1) + (int)((e1 >> 35) & 1);
+            if (e0 & CLC_PENDING) {
+                // e0 = UPDATE_BEFORE(top, a source row), e1 = UPDATE_AFTER
+                // (merged, a main-output row)
+                const uint32_t a = (uint32_t)e0;
+                const int rb = (int)(a >> PMH_ROW_BITS) * n_cols;
+                const uint64_t xa = a & PMH_ROW_MASK;
+                const uint64_t xb = (uint64_t)(ob + (uint32_t)e1);
+                bool eq = true;
+                for (int c0 = first_val; eq && c0 < n_cols; c0 += FOLD_CL_G) {
+                    // the group's validity bytes and values, all in flight
+                    // before the first compare
+                    uint8_t va[FOLD_CL_G], vb[FOLD_CL_G];
+                    int64_t pa[FOLD_CL_G], pb[FOLD_CL_G];
+#pragma unroll
+                    for (int j = 0; j < FOLD_CL_G; j++) {
+                        const int c = c0 + j < n_cols ? c0 + j : n_cols - 1;
+                        const int w = t.width[c];
+                        va[j] = fold_cl_validity(t, c, true, rb, xa);
+                        vb[j] = fold_cl_validity(t, c, false, 0, xb);
+                        pa[j] = w ? fold_cl_value(t, c, w, true, rb, xa) : 0;
+                        pb[j] = w ? fold_cl_value(t, c, w, false, 0, xb) : 0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < FOLD_CL_G; j++)
+                        if ((va[j] != 0) != (vb[j] != 0) ||
+                            (va[j] && pa[j] != pb[j]))
+                            eq = false;
+                }
+                if (eq) nv = 0;
+            }
+            verd |= (uint32_t)nv << (2 * (g - lo));
+            nrows += nv;
+        }
+        int32_t incl = nrows;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) wave_tot[buf][wv] = incl;
+        __syncthreads();
+        int32_t add = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const int32_t x = wave_tot[buf][w];
+            if (w < wv) add += x;
+            tot += x;
+        }
+        int32_t o = add + incl - nrows;
+        for (int32_t g = lo; g < hi; g++) {
+            const int nv = (verd >> (2 * (g - lo))) & 3;
+            if (nv >= 1) out[o++] = in[2 * g];
+            if (nv == 2) out[o++] = in[2 * g + 1];
+        }
+        if (tid == 0) cl_counts[tile] = tot;
+    }
+}
+
+// Write the compacted rows into the changelog output columns. A before-type
+// row gathers key, sequence number, values and validity from its source
+// record, an after-type row copies them from the main output row; the kind
+// column takes the changelog RowKind of the entry. Columns go in groups of
+// FOLD_CL_G: a row's loads of the group are issued before its stores.
+__launch_bounds__(FOLD_CL_THREADS) __global__
+void k_cl_emit_out(const DevCol *cols, const uint8_t *col_dtype,
+                   const uint8_t *col_nullable, int n_cols, int k,
+                   int kind_col, const uint64_t *cl_rows,
+                   const int32_t *cl_counts, const int64_t *cl_offsets,
+                   const int64_t *tile_offsets, int64_t n_tiles,
+                   int64_t tile_rows, void *const *out_ptrs,
+                   uint8_t *const *out_valid, void *const *out_ptrs2,
+                   uint8_t *const *out_valid2) {
+    extern __shared__ uint64_t fold_smem[];
+    const FoldClTables t =
+        fold_cl_stage(fold_smem, cols, col_dtype, col_nullable, n_cols, k,
+                      out_ptrs, out_valid, out_ptrs2, out_valid2);
+    const int64_t cap2 = 2 * (tile_rows + PMH_MAX_RUNS);
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t *in = &cl_rows[tile * cap2];
+        int32_t n = cl_counts[tile];
+        n = n < 0 ? 0 : (n > cap2 ? (int32_t)cap2 : n);
+        const int64_t ob = cl_offsets[tile];
+        const int64_t mb = tile_offsets[tile];
+        for (int32_t i = threadIdx.x; i < n; i += FOLD_CL_THREADS) {
+            const uint64_t e = in[i];
+            const bool src = !(e & CLC_FROM_OUT);
+            const uint32_t m = (uint32_t)e;
+            const int rb = src ? (int)(m >> PMH_ROW_BITS) * n_cols : 0;
+            const uint64_t row =
+                src ? (uint64_t)(m & PMH_ROW_MASK) : (uint64_t)(mb + m);
+            const int8_t kd = (int8_t)((e >> CLC_KIND_SHIFT) & 7);
+            const uint64_t o = (uint64_t)(ob + i);
+            for (int c0 = 0; c0 < n_cols; c0 += FOLD_CL_G) {
+                uint8_t vb[FOLD_CL_G];
+                int64_t v[FOLD_CL_G];
+#pragma unroll
+                for (int j = 0; j < FOLD_CL_G; j++) {
+                    const int c = c0 + j < n_cols ? c0 + j : n_cols - 1;
+                    const int w = t.width[c];
+                    vb[j] = fold_cl_validity(t, c, src, rb, row);
+                    v[j] = c == kind_col ? (int64_t)kd
+                           : w ? fold_cl_value(t, c, w, src, rb, row)
+                               : 0;
+                }
+#pragma unroll
+                for (int j = 0; j < FOLD_CL_G; j++) {
+                    const int c = c0 + j;
+                    if (c >= n_cols) break;
+                    const int w = t.width[c];
+                    if (t.ov2[c]) gstore<uint8_t>(t.ov2[c] + o, vb[j]);
+                    const uint64_t d = t.out2[c];
+                    if (c == kind_col || w == 1)
+                        gstore<int8_t>(d + o, (int8_t)v[j]);
+                    else if (w == 2)
+                        gstore<int16_t>(d + o * 2, (int16_t)v[j]);
+                    else if (w == 4)
+                        gstore<int32_t>(d + o * 4, (int32_t)v[j]);
+                    else if (w == 8)
+                        gstore<int64_t>(d + o * 8, v[j]);
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------ k_zstd_pages
 //
 // On-GPU zstd page decompression: one WAVEFRONT per parquet
@@ -4751,6 +5087,8 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
         constexpr bool TB = decltype(tb)::value;
         if (lk)
             launch(k_merge_tiles<false, false, true, KM, TB>);  // dedup only
+        else if (pu && (flags & PMH_FLAG_FOLD_CL))
+            launch(k_merge_tiles<true, false, false, KM, TB, true>);
         else if (pu)
             launch(k_merge_tiles<true, false, false, KM, TB>);  // never FR
         else if (fr)
@@ -5050,6 +5388,43 @@ hipError_t pmh_launch_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
                        col_dtype, col_nullable, n_cols, kind_col, cl_rows,
                        cl_counts, cl_offsets, n_tiles, tile_rows, out_ptrs,
                        out_valid);
+    return hipGetLastError();
+}
+
+hipError_t pmh_launch_cl_finalize_out(
+    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
+    int n_cols, int first_val, int k, const uint64_t *cl_entries,
+    uint64_t *cl_out, int32_t *cl_counts, const int64_t *tile_offsets,
+    int64_t n_tiles, int64_t tile_rows, void *const *out_ptrs,
+    uint8_t *const *out_valid, hipStream_t stream) {
+    const int64_t lds = pmh_fold_cl_lds(k, n_cols);
+    // a thread keeps its pairs' verdicts in one 32-bit register
+    if (lds > PMH_FOLD_CL_LDS_MAX ||
+        tile_rows + PMH_MAX_RUNS > 16 * FOLD_CL_THREADS)
+        return hipErrorInvalidValue;
+    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
+    hipLaunchKernelGGL(k_cl_finalize_out, dim3(blocks), dim3(FOLD_CL_THREADS),
+                       (size_t)lds, stream, cols, col_dtype, col_nullable,
+                       n_cols, first_val, k, cl_entries, cl_out, cl_counts,
+                       tile_offsets, n_tiles, tile_rows, out_ptrs, out_valid);
+    return hipGetLastError();
+}
+
+hipError_t pmh_launch_cl_emit_out(
+    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
+    int n_cols, int k, int kind_col, const uint64_t *cl_rows,
+    const int32_t *cl_counts, const int64_t *cl_offsets,
+    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
+    void *const *out_ptrs, uint8_t *const *out_valid, void *const *out_ptrs2,
+    uint8_t *const *out_valid2, hipStream_t stream) {
+    const int64_t lds = pmh_fold_cl_lds(k, n_cols);
+    if (lds > PMH_FOLD_CL_LDS_MAX) return hipErrorInvalidValue;
+    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
+    hipLaunchKernelGGL(k_cl_emit_out, dim3(blocks), dim3(FOLD_CL_THREADS),
+                       (size_t)lds, stream, cols, col_dtype, col_nullable,
+                       n_cols, k, kind_col, cl_rows, cl_counts, cl_offsets,
+                       tile_offsets, n_tiles, tile_rows, out_ptrs, out_valid,
+                       out_ptrs2, out_valid2);
     return hipGetLastError();
 }
 

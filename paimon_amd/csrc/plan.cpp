@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/paimon_hip.h"
+#include "changelog_core.h"
 #include "codec.h"
 #include "zstd_core.h"
 #include <map>
@@ -735,6 +736,9 @@ struct pmh_plan_t {
     // Wrapper): a second output stream of changelog rows per read_next
     bool changelog = false;
     bool cl_row_dedup = false;
+    // full-compaction changelog of a folding engine (partial-update /
+    // aggregation): after-type rows come from the main output
+    bool cl_fold = false;
     int max_level = 0;
     // changelog-producer = lookup (LookupChangelogMergeFunctionWrapper):
     // the levels above the compaction's output level, one sorted run per
@@ -3371,11 +3375,15 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                               "FullChangelogMergeFunctionWrapper maxLevel)");
                     return nullptr;
                 }
-                if (plan->pu || plan->agg) {
-                    set_error("changelog_producer=full-compaction is "
-                              "supported for deduplicate/first-row in v1 "
-                              "(partial-update/aggregation changelog is a "
-                              "later round)");
+                // partial-update / aggregation: the folded changelog chain
+                // (k_cl_finalize_out / k_cl_emit_out read the merged row
+                // from the main output)
+                plan->cl_fold = plan->pu;
+                if (plan->cl_fold && plan->ignore_delete) {
+                    set_error("changelog_producer=full-compaction with the "
+                              "%s engine cannot be combined with "
+                              "ignore_delete",
+                              plan->agg ? "aggregation" : "partial-update");
                     return nullptr;
                 }
             } else if (cp == "lookup") {
@@ -3696,6 +3704,23 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             }
             if (sec.hier && !build_hier_section(plan.get(), sec))
                 return nullptr;
+            if (plan->cl_fold) {
+                // the folded changelog kernels keep per-run column tables in
+                // LDS and address columns directly
+                const int64_t lds = pmh_fold_cl_lds(
+                    (int64_t)sec.runs.size(), (int64_t)plan->cols.size());
+                if (!sec.cols_contig || lds > PMH_FOLD_CL_LDS_MAX) {
+                    set_error("changelog_producer=full-compaction with the "
+                              "%s engine: a section of %zu runs x %zu columns "
+                              "needs %lld bytes of column tables (limit %lld) "
+                              "and contiguous columns",
+                              plan->agg ? "aggregation" : "partial-update",
+                              sec.runs.size(), plan->cols.size(),
+                              (long long)lds,
+                              (long long)PMH_FOLD_CL_LDS_MAX);
+                    return nullptr;
+                }
+            }
             plan->rows_in_total += run_rows;
             plan->sections.push_back(std::move(sec));
         }
@@ -4122,6 +4147,13 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
         }
         goto collect;
     }
+    if (p->cl_fold && ((flags >> 8) & 0xf)) {
+        // an ablated merge leaves the changelog counts unwritten
+        set_error("PMH_ABLATE cannot be combined with a partial-update / "
+                  "aggregation changelog plan");
+        for (auto &evv : ev) (void)hipEventDestroy(evv);
+        return -1;
+    }
     if (p->lookup) {
         // point lookup into the upper levels for every level-0 row, before
         // the merge walk consumes the probe words (timed as lookup_ms)
@@ -4136,7 +4168,8 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
                                sec.lens_dev, k, sec.cuts, n_tiles_eff,
                                PMH_TILE_ROWS,
                                flags | (p->cl_row_dedup ? 128 : 0) |
-                                   (p->lookup ? PMH_FLAG_LOOKUP : 0),
+                                   (p->lookup ? PMH_FLAG_LOOKUP : 0) |
+                                   (p->cl_fold ? PMH_FLAG_FOLD_CL : 0),
                                sec.tombs_dev, sec.winners,
                                sec.tile_counts, sec.group_start, sec.err_dev,
                                sec.run_levels, p->max_level, sec.cl_entries,
@@ -4182,7 +4215,24 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
                             p->out_valid_dev, st);
     }
     if (e != hipSuccess) return fail("emit", e);
-    if (p->changelog) {
+    if (p->cl_fold) {
+        // folded chain: the merged rows are in the main output by now
+        e = pmh_launch_cl_finalize_out(
+            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols,
+            p->n_key_cols + 2, k, sec.cl_entries, sec.cl_rows, sec.cl_counts,
+            sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS, p->out_ptrs_dev,
+            p->out_valid_dev, st);
+        if (e != hipSuccess) return fail("cl_finalize_out", e);
+        e = pmh_launch_scan_tiles(sec.cl_counts, n_tiles_eff, sec.cl_offsets,
+                                  sec.cl_total_dev, st);
+        if (e != hipSuccess) return fail("cl_scan", e);
+        e = pmh_launch_cl_emit_out(
+            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols, k,
+            p->n_key_cols + 1, sec.cl_rows, sec.cl_counts, sec.cl_offsets,
+            sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS, p->out_ptrs_dev,
+            p->out_valid_dev, p->out_ptrs2_dev, p->out_valid2_dev, st);
+        if (e != hipSuccess) return fail("cl_emit_out", e);
+    } else if (p->changelog) {
         e = pmh_launch_cl_finalize(sec.all_cols, p->col_dtype_dev, n_cols,
                                    p->n_key_cols + 2, k, sec.cl_entries,
                                    sec.cl_rows, sec.cl_counts, n_tiles_eff,
@@ -5224,6 +5274,35 @@ int pmh_debug_lookup_probe(int n_levels, const int64_t *const *level_keys,
             out_level[i] = l;
             out_row[i] = l < 0 ? -1 : row;
         }
+    }
+    return 0;
+}
+
+int pmh_debug_changelog_decide(int64_t n_groups, const int32_t *nlive,
+                               const int32_t *n_top,
+                               const uint8_t *merged_is_add, int pending,
+                               int32_t *out_n, int8_t *out_kinds,
+                               uint8_t *out_after_is_merged,
+                               uint8_t *out_pending) {
+    if (n_groups < 0 ||
+        (n_groups > 0 && (!nlive || !n_top || !merged_is_add || !out_n ||
+                          !out_kinds))) {
+        set_error("pmh_debug_changelog_decide: bad arguments");
+        return -1;
+    }
+    for (int64_t g = 0; g < n_groups; g++) {
+        if (nlive[g] < 1 || n_top[g] < 0 || n_top[g] > nlive[g]) {
+            set_error("pmh_debug_changelog_decide: group %lld is malformed "
+                      "(nlive >= 1, 0 <= n_top <= nlive)", (long long)g);
+            return -1;
+        }
+        const ClcDecision d = clc_decide(nlive[g], n_top[g],
+                                         merged_is_add[g] != 0, pending != 0);
+        out_n[g] = d.n;
+        out_kinds[2 * g] = (int8_t)(d.n >= 1 ? d.kind0 : -1);
+        out_kinds[2 * g + 1] = (int8_t)(d.n == 2 ? d.kind1 : -1);
+        if (out_after_is_merged) out_after_is_merged[g] = d.after_is_merged;
+        if (out_pending) out_pending[g] = d.pending;
     }
     return 0;
 }
