@@ -437,6 +437,11 @@ int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
                         int key_width, int64_t tile_rows, int mode,
                         int32_t *cuts_out);
 
+/* Which kernel the last winner emit of this process ran: 0 none yet, 1 the
+ * paged k_emit, 2 k_emit_contig (gathers), 3 k_emit_stream (tile slices
+ * streamed through LDS). Lets a test tell a streamed read from a fallback. */
+int pmh_debug_last_emit_kernel(void);
+
 /* Parse one JSON number the way the plan descriptor's numbers are parsed
  * (minKey/maxKey, rowCount, integer filter literals): a token without '.',
  * 'e' or 'E' is an exact int64, a fractional token rounds to nearest, an

@@ -257,14 +257,29 @@ hipError_t pmh_launch_emit_dense(const DevCol *cols,
                                  uint8_t *const *out_valid,
                                  hipStream_t stream);
 
+// The kernel the last pmh_launch_emit chose.
+enum {
+    PMH_EMIT_NONE = 0,
+    PMH_EMIT_PAGED = 1,   // k_emit
+    PMH_EMIT_CONTIG = 2,  // k_emit_contig
+    PMH_EMIT_STREAM = 3,  // k_emit_stream
+};
+int pmh_last_emit_kernel();
+
 // Winner gather. n_desc = run slots of `cols` that a winner word can name
 // (the k merge runs plus a lookup plan's level slots); contiguous = every one
-// of those n_desc * n_cols descriptors has n_pages == 1. Contiguous plans
-// whose descriptor table fits LDS run k_emit_contig; the rest, and
-// PMH_EMIT_LEGACY=1, run the paged k_emit.
+// of those n_desc * n_cols descriptors has n_pages == 1. cuts / lens are the
+// partition's cuts ((n_tiles + 1) * k) and the k run lengths the winners
+// were merged from; any_nullable = some column of the plan has a validity
+// output. Contiguous plans without lookup slots (n_desc == k) and without
+// nullable columns stream their tile slices through LDS (k_emit_stream,
+// PMH_EMIT_STREAM=0 turns it off); other contiguous plans whose descriptor
+// table fits LDS run k_emit_contig; the rest, and PMH_EMIT_LEGACY=1, run the
+// paged k_emit.
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
-                           const uint8_t *col_nullable, int n_cols, int k,
-                           int n_desc, int contiguous,
+                           const uint8_t *col_nullable, int any_nullable,
+                           int n_cols, int k, int n_desc, int contiguous,
+                           const int32_t *cuts, const int64_t *lens,
                            const uint32_t *winners,
                            const int32_t *tile_counts,
                            const int64_t *tile_offsets, int64_t n_tiles,

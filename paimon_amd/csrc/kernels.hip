@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "changelog_core.h"
+#include "emit_stream_core.h"
 #include "kernels.h"
 #include "lookup_core.h"
 #include "partition_core.h"
@@ -2539,6 +2540,290 @@ void k_emit_contig(const DevCol *cols /* n_desc * n_cols, run-major */,
             lists(std::true_type{});
         else
             lists(std::false_type{});
+    }
+}
+
+// ------------------------------------------------------ k_emit_stream
+//
+// Emit without a gather. The winners of tile t that come from run r all lie
+// in the slice of run r that k_merge_tiles staged for that tile, so a block
+// takes one tile at a time (grid-stride) and, per group of columns,
+//  1. loads the tile's per-run slices of the group's columns the way
+//     tile_prefetch loads key / seq / kind: consecutive lanes read
+//     consecutive rows, dead slots clamp to the last element, everything
+//     issued back to back into registers;
+//  2. puts them into LDS at the merge's own flat slot;
+//  3. has each output row read its winner's slot and store coalesced at
+//     out[c] + (tile_offsets[t] + j) * width.
+// The 28 % losers of the flagship shape are read too; what goes away is one
+// L2 request per 20-30 useful bytes of a 4-byte column and a 64-bit address
+// per gather in flight (profiles/emit_stream_phases.md).
+// Pipelining: one register set. As soon as a group's registers are in LDS the
+// next group's loads (at a tile's last group: the next tile's setup, winner
+// words and first group) are issued, ahead of this group's permute and
+// stores. The slot mapping and the group plan are emit_stream_core.h's.
+// Columns are ordered into lists by output width exactly as in k_emit_contig;
+// a group never spans two lists. Validity is not streamed: the launcher
+// sends a plan with a nullable emitted column to k_emit_contig.
+// Barriers: three in the prologue, two per group; all block-uniform.
+constexpr int EMS_THREADS = PMH_TILE_THREADS;
+constexpr int EMS_ITER = PMH_TILE_ITER;
+constexpr int64_t EMS_LDS_DEFAULT = 60 * 1024;  // data bytes per block
+
+// LDS bytes of k_emit_stream's tables, ahead of the data area
+__host__ __device__ static inline int64_t emit_stream_tables(int64_t k,
+                                                             int64_t n_cols) {
+    const int64_t b = 8 * k * n_cols + 8 * n_cols + 32 +
+                      2 * (n_cols + 1) + 3 * n_cols;
+    return (b + 15) & ~(int64_t)15;
+}
+
+// The group loop's body is full of values that do not change from group to
+// group (slot * width + LDS base, tid * width, ... for every slot and every
+// width). Hoisted out of the loop they cost more registers than the kernel
+// has (230 VGPRs unbounded, 440 bytes of scratch per lane at 128); an empty
+// asm on the per-thread inputs keeps the derived values inside the loop.
+template <typename T>
+DEV T ems_keep(T x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// W-byte loads of a group's n columns (list positions p ...) for this
+// thread's slots; an 8-byte column takes two of the 32-bit register rows.
+template <int W, int GU>
+DEV void ems_load(const uint64_t *s_addr, int p, int n, int n_cols,
+                  const uint32_t (&src)[EMS_ITER],
+                  uint32_t (&v)[GU][EMS_ITER]) {
+#pragma unroll
+    for (int g = 0; g < GU * 4 / W; g++) {
+        if (g >= n) break;  // block-uniform
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s++) {
+            const uint32_t sr = ems_keep(src[s]);  // run:5 | row:27
+            const uint64_t a =
+                s_addr[(sr >> PMH_ROW_BITS) * (uint32_t)n_cols + p + g] +
+                (uint64_t)((sr & PMH_ROW_MASK) * (uint32_t)W);
+            if constexpr (W == 8) {
+                const uint64_t x = gload<uint64_t>(a);
+                v[2 * g][s] = (uint32_t)x;
+                v[2 * g + 1][s] = (uint32_t)(x >> 32);
+            } else {
+                v[g][s] = gload<uint32_t>(a);
+            }
+        }
+        // one column's lookups and addresses live at a time (registers),
+        // as in tile_prefetch; every load is still issued before any wait
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// registers -> LDS at slot tid + s * EMS_THREADS; column g at g * TILE_MAX
+template <int W, int GU>
+DEV void ems_fill(uint8_t *buf, int n, int32_t m, int tid,
+                  const uint32_t (&v)[GU][EMS_ITER]) {
+#pragma unroll
+    for (int g = 0; g < GU * 4 / W; g++) {
+        if (g >= n) break;
+        const int32_t t = ems_keep(tid);
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s++) {
+            const int32_t e = t + s * EMS_THREADS;
+            if (e >= m) continue;
+            uint8_t *d = buf + ((size_t)g * PMH_TILE_MAX + e) * W;
+            if constexpr (W == 8)
+                *reinterpret_cast<uint64_t *>(d) =
+                    ((uint64_t)v[2 * g + 1][s] << 32) | v[2 * g][s];
+            else
+                *reinterpret_cast<uint32_t *>(d) = v[g][s];
+        }
+    }
+}
+
+// output row j = tid + s * EMS_THREADS reads its winner's slot and stores,
+// narrowing to S as k_emit_contig's lists do
+template <typename L, typename S>
+DEV void ems_permute(const uint8_t *buf, const uint64_t *s_out, int p, int n,
+                     int64_t toff, int32_t count, int tid,
+                     const uint32_t (&wslot)[EMS_ITER / 2]) {
+    for (int g = 0; g < n; g++) {
+        const uint64_t ob =
+            uniform64(s_out[p + g] + (uint64_t)toff * sizeof(S));
+        const uint8_t *cb = buf + (size_t)g * PMH_TILE_MAX * sizeof(L);
+        const int32_t t = ems_keep(tid);
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s++) {
+            const int32_t j = t + s * EMS_THREADS;
+            if (j >= count) continue;
+            const L x = *reinterpret_cast<const L *>(
+                cb + (size_t)((ems_keep(wslot[s / 2]) >> (16 * (s & 1))) &
+                              0xffffu) *
+                         sizeof(L));
+            const uint64_t oa =
+                ob + (uint64_t)((uint32_t)t * (uint32_t)sizeof(S)) +
+                (uint64_t)(s * EMS_THREADS * (int)sizeof(S));
+            gstore<S>(oa, (S)x);
+        }
+    }
+}
+
+template <int KM, int GU>
+__attribute__((amdgpu_waves_per_eu(4))) __launch_bounds__(EMS_THREADS, 2)
+__global__
+void k_emit_stream(const DevCol *cols /* k * n_cols, run-major */,
+                   const uint8_t *col_dtype, int n_cols, int n_emit, int k,
+                   const int32_t *__restrict__ cuts,
+                   const int64_t *__restrict__ lens,
+                   const uint32_t *__restrict__ winners,
+                   const int32_t *__restrict__ tile_counts,
+                   const int64_t *__restrict__ tile_offsets, int64_t n_tiles,
+                   int64_t tile_rows, void *const *out_ptrs,
+                   int lds_budget) {
+    extern __shared__ uint64_t ems_smem[];
+    const int n_ent = k * n_cols;
+    uint64_t *s_addr = ems_smem;                    // [n_ent] run, position
+    uint64_t *s_out = s_addr + n_ent;               // [n_cols] by position
+    int *s_cnt = (int *)(s_out + n_cols);           // list lengths, n groups
+    uint16_t *s_bound = (uint16_t *)(s_cnt + 8);    // [n_cols + 1] groups
+    uint8_t *s_pos = (uint8_t *)(s_bound + n_cols + 1);  // column -> position
+    uint8_t *s_cls = s_pos + n_cols;                // [n_cols] by column
+    uint8_t *s_clsp = s_cls + n_cols;               // [n_cols] by position
+    uint8_t *buf =
+        (uint8_t *)ems_smem + emit_stream_tables(k, n_cols);  // data area
+
+    const int tid = threadIdx.x;
+    // the lists, as in k_emit_contig
+    auto dt_class = [](int dt) {
+        return dt == 1 ? 1
+               : dt == 2 ? 2
+               : (dt == 3 || dt == 5 || dt == 7) ? 4
+               : (dt == 4 || dt == 6) ? 8
+                                      : 0;
+    };
+    for (int c = tid; c < n_cols; c += EMS_THREADS)
+        s_cls[c] = c < n_emit ? dt_class(col_dtype[c]) : 0;
+    __syncthreads();
+    for (int c = tid; c < n_cols; c += EMS_THREADS) {
+        const int cls = s_cls[c];
+        int n_of[4] = {0, 0, 0, 0};  // list lengths, by log2(width)
+        int before = 0;
+        for (int j = 0; j < n_cols; j++) {
+            const int cj = s_cls[j];
+#pragma unroll
+            for (int w = 0; w < 4; w++) n_of[w] += cj == (1 << w);
+            before += (j < c && cj == cls);
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) s_cnt[w] = n_of[w];
+        }
+        if (cls) {
+            int p = before;
+#pragma unroll
+            for (int w = 0; w < 3; w++) p += (1 << w) < cls ? n_of[w] : 0;
+            s_pos[c] = (uint8_t)p;
+            s_clsp[p] = (uint8_t)cls;
+            s_out[p] = (uint64_t)out_ptrs[c];
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < n_ent; e += EMS_THREADS) {
+        const int r = e / n_cols, c = e - r * n_cols;
+        if (!s_cls[c]) continue;
+        s_addr[r * n_cols + s_pos[c]] = cols[e].addr0;
+    }
+    if (tid == 0)
+        s_cnt[4] = esc_plan_groups(
+            s_clsp, nullptr, s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3],
+            PMH_TILE_MAX, lds_budget, GU, GU / 2, s_bound);
+    __syncthreads();
+    const int ng = s_cnt[4];
+    int64_t tile = blockIdx.x;
+    if (ng <= 0 || tile >= n_tiles) return;  // block-uniform
+
+    const int64_t wstride = tile_rows + PMH_MAX_RUNS;
+    EscTile<KM> ts;
+    uint32_t src[EMS_ITER];  // this thread's slots: run:5 | row:27
+    uint32_t wraw[EMS_ITER], v[GU][EMS_ITER];
+    uint32_t wslot[EMS_ITER / 2];  // its output rows' slots, 16 bits each
+    int32_t count_n;
+    int64_t toff_n;
+    // tile t's segments, this thread's slot sources, its winner words
+    auto setup = [&](int64_t t) {
+        // opaque, or everything below that depends on the next tile's index
+        // alone is hoisted out of the group loop and held in registers
+        asm volatile("" : "+s"(t));
+        esc_tile_setup<KM>(cuts + t * k, cuts + (t + 1) * k, lens, k, ts);
+        count_n = tile_counts[t];
+        toff_n = tile_offsets[t];
+        const int32_t last = ts.mtotal > 0 ? ts.mtotal - 1 : 0;
+        const int32_t tk = ems_keep(tid);
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s++) {
+            const int32_t x = tk + s * EMS_THREADS;
+            int run;
+            uint32_t row;
+            esc_slot_source<KM>(ts, k, x < last ? x : last, &run, &row);
+            src[s] = ((uint32_t)run << PMH_ROW_BITS) | row;
+        }
+        const uint64_t wb = (uint64_t)(winners + t * wstride);
+        const uint32_t wlast = (uint32_t)wstride - 1;  // past it: no winner
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s++) {
+            const uint32_t j = (uint32_t)(tk + s * EMS_THREADS);
+            wraw[s] = gload<uint32_t>(wb + (j < wlast ? j : wlast) * 4u);
+        }
+    };
+    auto issue = [&](int gi) {
+        if (ts.mtotal <= 0) return;  // no element, no valid address
+        const int p = s_bound[gi], n = s_bound[gi + 1] - p;
+        if (s_clsp[p] == 8) ems_load<8, GU>(s_addr, p, n, n_cols, src, v);
+        else ems_load<4, GU>(s_addr, p, n, n_cols, src, v);
+    };
+    setup(tile);
+    issue(0);
+    for (;;) {
+        const int32_t count = count_n;
+        const int64_t toff = toff_n;
+        // a slot is < PMH_TILE_MAX < 2^16 for every live row; the words
+        // past the tile's count are not winners and their slots go unread
+#pragma unroll
+        for (int s = 0; s < EMS_ITER; s += 2) {
+            const uint32_t lo = (uint32_t)esc_winner_slot<KM>(
+                ts, wraw[s] >> PMH_ROW_BITS, wraw[s] & PMH_ROW_MASK);
+            const uint32_t hi = (uint32_t)esc_winner_slot<KM>(
+                ts, wraw[s + 1] >> PMH_ROW_BITS, wraw[s + 1] & PMH_ROW_MASK);
+            wslot[s / 2] = (lo & 0xffffu) | (hi << 16);
+        }
+        const int64_t next = tile + gridDim.x;
+        for (int gi = 0; gi < ng; gi++) {
+            const int p = s_bound[gi], n = s_bound[gi + 1] - p;
+            const int cls = s_clsp[p];
+            if (cls == 8) ems_fill<8, GU>(buf, n, ts.mtotal, tid, v);
+            else ems_fill<4, GU>(buf, n, ts.mtotal, tid, v);
+            if (gi + 1 < ng) {
+                issue(gi + 1);
+            } else if (next < n_tiles) {
+                setup(next);
+                issue(0);
+            }
+            __syncthreads();
+            if (cls == 1)
+                ems_permute<int32_t, int8_t>(buf, s_out, p, n, toff,
+                                                 count, tid, wslot);
+            else if (cls == 2)
+                ems_permute<int32_t, int16_t>(buf, s_out, p, n, toff,
+                                                  count, tid, wslot);
+            else if (cls == 4)
+                ems_permute<int32_t, int32_t>(buf, s_out, p, n, toff,
+                                                  count, tid, wslot);
+            else
+                ems_permute<int64_t, int64_t>(buf, s_out, p, n, toff,
+                                                  count, tid, wslot);
+            __syncthreads();
+        }
+        if (next >= n_tiles) break;
+        tile = next;
     }
 }
 
@@ -5269,9 +5554,23 @@ hipError_t pmh_launch_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
     return hipGetLastError();
 }
 
+// which kernel the last pmh_launch_emit chose (PMH_EMIT_*); tests tell a
+// streamed read from a fallback by it
+static int g_last_emit_kernel = PMH_EMIT_NONE;
+int pmh_last_emit_kernel() { return g_last_emit_kernel; }
+
+// Winner emit. Three kernels, most specific first:
+//  - k_emit_stream (tile slices streamed through LDS, no gather) when the
+//    plan is all-contiguous, every run slot a winner can name is a merge run
+//    (n_desc == k: a lookup winner may name a slot outside the tile's
+//    slices), n_cols <= 256, no emitted column is nullable (validity is not
+//    streamed), the tables fit, and PMH_EMIT_STREAM is not 0;
+//  - k_emit_contig for the other all-contiguous plans whose tables fit;
+//  - k_emit for the rest, and under PMH_EMIT_LEGACY=1.
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
-                           const uint8_t *col_nullable, int n_cols, int k,
-                           int n_desc, int contiguous,
+                           const uint8_t *col_nullable, int any_nullable,
+                           int n_cols, int k, int n_desc, int contiguous,
+                           const int32_t *cuts, const int64_t *lens,
                            const uint32_t *winners,
                            const int32_t *tile_counts,
                            const int64_t *tile_offsets, int64_t n_tiles,
@@ -5302,6 +5601,49 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
     const bool contig = contiguous && n_desc >= 1 && n_cols <= 256 &&
                         lds <= EMIT_LDS_MAX &&
                         env_int("PMH_EMIT_LEGACY", 0) == 0;
+    const int64_t tables = emit_stream_tables(k, n_cols);
+    const bool streamed = contig && n_desc == k && !any_nullable &&
+                          tables <= EMIT_LDS_MAX && cuts && lens &&
+                          tile_rows == PMH_TILE_ROWS &&
+                          env_int("PMH_EMIT_STREAM", 1) != 0;
+    if (streamed) {
+        // PMH_EMIT_STREAM_LDS: data bytes per block. It sets the columns per
+        // group: 4 four-byte or 2 eight-byte ones at the default (two blocks
+        // per CU), half that below two 8-byte columns' worth. The sweep is in
+        // profiles/emit_stream_phases.md; one 8-byte column is the floor.
+        int64_t budget = env_int("PMH_EMIT_STREAM_LDS", (int)EMS_LDS_DEFAULT);
+        const int64_t col8 = (int64_t)PMH_TILE_MAX * 8;
+        if (budget < col8) budget = col8;
+        if (budget > EMS_LDS_DEFAULT) budget = EMS_LDS_DEFAULT;
+        // tables + data stay within the 64 KB a launch gets without asking
+        // (tables <= EMIT_LDS_MAX, so one 8-byte column always fits)
+        if (budget > 64 * 1024 - tables) budget = 64 * 1024 - tables;
+        const int gu = budget >= 2 * col8 ? 4 : 2;
+        int64_t max_blocks = 4096;  // k_merge_tiles' grid, see there
+        if (const char *e = getenv("PMH_EMIT_STREAM_BLOCKS")) {
+            const long long v = atoll(e);
+            if (v >= 1 && v <= 65535) max_blocks = v;
+        }
+        const int blocks = n_tiles < max_blocks ? (int)n_tiles : (int)max_blocks;
+        const size_t bytes = (size_t)(tables + budget);
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(EMS_THREADS), bytes,
+                               stream, cols, col_dtype, n_cols, n_emit, k,
+                               cuts, lens, winners, tile_counts, tile_offsets,
+                               n_tiles, tile_rows, out_ptrs, (int)budget);
+        };
+        auto launch_g = [&](auto km) {
+            constexpr int KM = decltype(km)::value;
+            if (gu == 2) launch(k_emit_stream<KM, 2>);
+            else launch(k_emit_stream<KM, 4>);
+        };
+        if (k <= 8) launch_g(std::integral_constant<int, 8>{});
+        else if (k <= 16) launch_g(std::integral_constant<int, 16>{});
+        else launch_g(std::integral_constant<int, PMH_MAX_RUNS>{});
+        g_last_emit_kernel = PMH_EMIT_STREAM;
+        return hipGetLastError();
+    }
+    g_last_emit_kernel = contig ? PMH_EMIT_CONTIG : PMH_EMIT_PAGED;
     if (contig) {
         auto launch = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(EMIT_THREADS), (size_t)lds,

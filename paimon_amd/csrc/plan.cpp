@@ -4008,6 +4008,8 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
     }
     int64_t n_tiles_eff = sec.n_tiles;
     int64_t rows_eff = sec.total_rows;
+    int any_nullable = 0;  // validity outputs keep emit off the streamed kernel
+    for (bool nb : p->col_nullable) any_nullable |= nb ? 1 : 0;
     if (sec.hier) {
         // batch pass: merge run batches into the virtual runs
         // (winner-of-winners — the dedup/first-row fold is associative;
@@ -4036,7 +4038,8 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
             if (hb != hipSuccess) return fail("hier scan", hb);
             hb = pmh_launch_emit(sec.rall + (size_t)lo * n_cols,
                                  p->hier_dtype_dev, p->col_nullable_dev,
-                                 n_cols, kb, kb, sec.cols_contig,
+                                 any_nullable, n_cols, kb, kb,
+                                 sec.cols_contig, sec.cuts, sec.rlens + lo,
                                  sec.winners, sec.tile_counts,
                                  sec.tile_offsets, btiles, PMH_TILE_ROWS,
                                  sec.lens_dev + b, sec.bout_ptrs[b],
@@ -4207,9 +4210,10 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
         // a lookup winner may name a lookup-level slot past the k merge
         // runs; a hierarchical chain reads its (contiguous) virtual runs
         e = pmh_launch_emit(sec.all_cols, p->col_dtype_dev,
-                            p->col_nullable_dev, n_cols, k,
+                            p->col_nullable_dev, any_nullable, n_cols, k,
                             sec.hier ? k : k + sec.n_lookup,
-                            sec.hier || sec.cols_contig, sec.winners,
+                            sec.hier || sec.cols_contig, sec.cuts,
+                            sec.lens_dev, sec.winners,
                             sec.tile_counts, sec.tile_offsets, n_tiles_eff,
                             PMH_TILE_ROWS, sec.total_dev, p->out_ptrs_dev,
                             p->out_valid_dev, st);
@@ -5306,6 +5310,8 @@ int pmh_debug_changelog_decide(int64_t n_groups, const int32_t *nlive,
     }
     return 0;
 }
+
+int pmh_debug_last_emit_kernel(void) { return pmh_last_emit_kernel(); }
 
 int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
                         int key_width, int64_t tile_rows, int mode,

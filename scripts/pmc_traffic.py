@@ -10,7 +10,9 @@ MI355X_MICROARCH.md §HBM:
     its exact algorithmic byte count);
   - 64B-granule gather reads are counted at request granularity -> raw
     (applies to k_emit's column gathers; its WRITE_SIZE raw has been
-    validated against the exact algorithmic output bytes).
+    validated against the exact algorithmic output bytes);
+  - k_emit_stream reads whole tile slices as coalesced streams -> x2, like
+    the merge kernel's staging.
 The result is the `roofline.traffic` calibration bench.py reports for the
 default workload.
 """
@@ -34,6 +36,10 @@ KERNELS = {
     "k_merge_tiles": ("merge", 2.0,
                       "FETCH x2 (wide coalesced staging, guide §HBM) + "
                       "WRITE raw"),
+    "k_emit_stream": ("emit", 2.0,
+                      "FETCH x2 (the tile slices of every column are read "
+                      "as wide coalesced streams, guide §HBM; no gathers "
+                      "left) + WRITE raw"),
     "k_emit<": ("emit", 1.0,
                 "FETCH raw (64B-granule gathers counted exactly) + WRITE "
                 "raw (validated = algorithmic output bytes)"),
@@ -57,7 +63,8 @@ def per_dispatch(pattern, counter, divisor=None):
 
 def match(averages):
     # ordered most-specific-first; first substring hit wins per kernel
-    order = ["k_merge_emit", "k_emit_dense", "k_merge_tiles", "k_emit"]
+    order = ["k_merge_emit", "k_emit_dense", "k_merge_tiles",
+             "k_emit_stream", "k_emit"]
     out = {}
     for kn, v in averages.items():
         if "_pu" in kn or "_agg" in kn:
