@@ -184,7 +184,7 @@ void pmh_close_session(pmh_session_t *s);
  * every level in "files"; files of one lookup level key-disjoint;
  * deduplicate engine only; a single integer key column; no ignore_delete,
  * no sequence fields, no PMH_FUSED=1, no deletionVector on a lookup file.
- * Staging (file read + H2D of encoded column chunks + page tables) happens
+ * Staging (file read + H2D of encoded column chunks + descriptors) happens
  * here; pmh_read_next launches only device work. */
 pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json);
 
@@ -437,9 +437,10 @@ int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
                         int key_width, int64_t tile_rows, int mode,
                         int32_t *cuts_out);
 
-/* Which kernel the last winner emit of this process ran: 0 none yet, 1 the
- * paged k_emit, 2 k_emit_contig (gathers), 3 k_emit_stream (tile slices
- * streamed through LDS). Lets a test tell a streamed read from a fallback. */
+/* Which kernel the last winner emit of this process ran: 0 none yet, 1
+ * k_emit (gathers, descriptors in global memory), 2 k_emit_contig (gathers,
+ * descriptors in LDS), 3 k_emit_stream (tile slices streamed through LDS).
+ * Lets a test tell a streamed read from a fallback. */
 int pmh_debug_last_emit_kernel(void);
 
 /* Parse one JSON number the way the plan descriptor's numbers are parsed

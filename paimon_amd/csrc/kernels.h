@@ -40,21 +40,14 @@ constexpr int PMH_TILE_MAX = PMH_TILE_ROWS + PMH_MAX_RUNS;
 constexpr int PMH_TILE_ITER =
     (PMH_TILE_MAX + PMH_TILE_THREADS - 1) / PMH_TILE_THREADS;
 
-// A decoded or raw-PLAIN region of one column of one run. Columns staged by
-// plan.cpp are CONTIGUOUS (n_pages == 1, direct addressing via addr0 — the
-// PLAIN page payloads are packed per column at H2D time); the paged path
-// (binary search by start_row) remains for future non-contiguous encodings.
-struct DevPage {
-    uint64_t addr;      // device pointer to first element
-    int64_t start_row;  // first run-row covered by this page
-};
-
+// One column of one run, as plan.cpp stages it: ONE contiguous device buffer
+// of `esize`-byte elements (the PLAIN page payloads are packed per column at
+// H2D time), addressed directly from addr0.
 struct DevCol {
-    uint64_t addr0;        // n_pages == 1 fast path: element 0 address
-    uint64_t valid0;       // byte-per-row validity array; 0 = all valid
-    const DevPage *pages;  // device array, sorted by start_row
-    int32_t n_pages;
-    int32_t esize;  // element size in bytes (stored width)
+    uint64_t addr0;   // element 0 address
+    uint64_t valid0;  // byte-per-row validity array; 0 = all valid
+    int32_t esize;    // element size in bytes (stored width)
+    int32_t pad;
 };
 
 // RleChunk, Rlev2Chunk, DeltaChunk, DeltaStream: stream_core.h (the host
@@ -119,9 +112,9 @@ hipError_t pmh_launch_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
 // (changelog_core.h). Both kernels therefore run after the engine's emit
 // kernel on the same stream and read out_ptrs / out_valid (the plan's main
 // output); emit writes out_ptrs2 / out_valid2. They stage pmh_fold_cl_lds(k,
-// n_cols) bytes of per-run column tables in LDS and need contiguous columns
-// (n_pages == 1); the launchers return hipErrorInvalidValue past
-// PMH_FOLD_CL_LDS_MAX (plan creation refuses such a section first).
+// n_cols) bytes of per-run column tables in LDS; the launchers return
+// hipErrorInvalidValue past PMH_FOLD_CL_LDS_MAX (plan creation refuses such a
+// section first).
 constexpr int PMH_FLAG_FOLD_CL = 1 << 16;
 constexpr int64_t PMH_FOLD_CL_LDS_MAX = 48 * 1024;
 constexpr int64_t pmh_fold_cl_lds(int64_t k, int64_t n_cols) {
@@ -260,25 +253,24 @@ hipError_t pmh_launch_emit_dense(const DevCol *cols,
 // The kernel the last pmh_launch_emit chose.
 enum {
     PMH_EMIT_NONE = 0,
-    PMH_EMIT_PAGED = 1,   // k_emit
+    PMH_EMIT_GATHER = 1,  // k_emit
     PMH_EMIT_CONTIG = 2,  // k_emit_contig
     PMH_EMIT_STREAM = 3,  // k_emit_stream
 };
 int pmh_last_emit_kernel();
 
 // Winner gather. n_desc = run slots of `cols` that a winner word can name
-// (the k merge runs plus a lookup plan's level slots); contiguous = every one
-// of those n_desc * n_cols descriptors has n_pages == 1. cuts / lens are the
+// (the k merge runs plus a lookup plan's level slots). cuts / lens are the
 // partition's cuts ((n_tiles + 1) * k) and the k run lengths the winners
 // were merged from; any_nullable = some column of the plan has a validity
-// output. Contiguous plans without lookup slots (n_desc == k) and without
-// nullable columns stream their tile slices through LDS (k_emit_stream,
-// PMH_EMIT_STREAM=0 turns it off); other contiguous plans whose descriptor
-// table fits LDS run k_emit_contig; the rest, and PMH_EMIT_LEGACY=1, run the
-// paged k_emit.
+// output. Plans without lookup slots (n_desc == k) and without nullable
+// columns stream their tile slices through LDS (k_emit_stream,
+// PMH_EMIT_STREAM=0 turns it off); other plans whose descriptor table fits
+// LDS run k_emit_contig; the rest, and PMH_EMIT_LEGACY=1, run k_emit, which
+// reads its descriptors from global memory.
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
                            const uint8_t *col_nullable, int any_nullable,
-                           int n_cols, int k, int n_desc, int contiguous,
+                           int n_cols, int k, int n_desc,
                            const int32_t *cuts, const int64_t *lens,
                            const uint32_t *winners,
                            const int32_t *tile_counts,

@@ -21,7 +21,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "../../include/paimon_hip.h"
 #include "changelog_core.h"
+#include "column_core.h"
 #include "emit_stream_core.h"
 #include "kernels.h"
 #include "lookup_core.h"
@@ -32,21 +34,91 @@
 
 namespace pmh {
 
-// ---------------------------------------------------------------- paged cols
+// ------------------------------------------------------------ column access
 
 template <typename T>
 DEV T col_load(const DevCol &c, int64_t row) {
-    if (c.n_pages == 1)  // staged columns are contiguous: direct addressing
-        return *reinterpret_cast<const T *>(c.addr0 + (uint64_t)row * sizeof(T));
-    // general paged path: last page with start_row <= row
-    int lo = 0, hi = c.n_pages - 1;
+    return *reinterpret_cast<const T *>(c.addr0 + (uint64_t)row * sizeof(T));
+}
+
+// validity byte of a row; a column without staged nulls is all valid
+DEV uint8_t col_valid(const DevCol &c, int64_t row) {
+    return c.valid0 ? ((const uint8_t *)c.valid0)[row] : 1;
+}
+
+// staged at 8 bytes; every other dtype is staged at 4 (pmh_stored_width)
+DEV bool dt_wide(int dt) { return dt == PMH_DT_INT64 || dt == PMH_DT_FLOAT64; }
+
+// a row's stored element as 64 bits (4-byte elements sign-extend)
+DEV int64_t col_load_wide(const DevCol &c, int64_t row, int dt) {
+    return dt_wide(dt) ? col_load<int64_t>(c, row)
+                       : (int64_t)col_load<int32_t>(c, row);
+}
+
+// packed winner / member word (run:5 | row:27): its column descriptor and row
+DEV const DevCol &member_col(const DevCol *cols, int n_cols, uint32_t m,
+                             int c) {
+    return cols[(m >> PMH_ROW_BITS) * n_cols + c];
+}
+DEV int64_t member_row(uint32_t m) { return m & PMH_ROW_MASK; }
+// the word's column c: validity byte, and stored element as 64 bits
+DEV uint8_t member_valid(const DevCol *cols, int n_cols, uint32_t m, int c) {
+    return col_valid(member_col(cols, n_cols, m, c), member_row(m));
+}
+DEV int64_t member_load(const DevCol *cols, int n_cols, uint32_t m, int c,
+                        int dt) {
+    return col_load_wide(member_col(cols, n_cols, m, c), member_row(m), dt);
+}
+// its row's packed validity mask (k_pack_valid: bit c = column c non-null)
+DEV uint64_t member_mask(uint64_t *const *run_masks, uint32_t m) {
+    return run_masks[m >> PMH_ROW_BITS][m & PMH_ROW_MASK];
+}
+
+// out[i] = bits, narrowed to the column's output width (pmh_out_width)
+DEV void out_store(void *out, int dt, int64_t i, int64_t bits) {
+    switch (dt) {
+    case PMH_DT_INT8: ((int8_t *)out)[i] = (int8_t)bits; break;
+    case PMH_DT_INT16: ((int16_t *)out)[i] = (int16_t)bits; break;
+    case PMH_DT_INT32:
+    case PMH_DT_FLOAT32:
+    case PMH_DT_STRING:  // string ids ride as int32
+        ((int32_t *)out)[i] = (int32_t)bits;
+        break;
+    case PMH_DT_INT64:
+    case PMH_DT_FLOAT64: ((int64_t *)out)[i] = bits; break;
+    }
+}
+
+// Contiguous output slice [slice_lo, slice_hi) of this block: `total` rows
+// dealt to the grid's blocks in equal shares (the last ones may be empty).
+DEV int64_t slice_rows(int64_t total) {
+    return (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
+}
+DEV int64_t slice_lo_of(int64_t total) {
+    return (int64_t)blockIdx.x * slice_rows(total);
+}
+DEV int64_t slice_hi_of(int64_t total) {
+    const int64_t hi = slice_lo_of(total) + slice_rows(total);
+    return hi < total ? hi : total;
+}
+
+// Tile cursor over tile_offsets (the exclusive scan of the tile counts):
+// tile_seek finds the tile that owns output rank i; tile_walk advances a
+// cursor t that is at or before that tile (ranks visited in ascending order).
+DEV int64_t tile_seek(const int64_t *tile_offsets, int64_t n_tiles,
+                      int64_t i) {
+    int64_t lo = 0, hi = n_tiles - 1;
     while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (c.pages[mid].start_row <= row) lo = mid;
+        int64_t mid = (lo + hi + 1) >> 1;
+        if (tile_offsets[mid] <= i) lo = mid;
         else hi = mid - 1;
     }
-    const DevPage &pg = c.pages[lo];
-    return *reinterpret_cast<const T *>(pg.addr + (uint64_t)(row - pg.start_row) * sizeof(T));
+    return lo;
+}
+DEV int64_t tile_walk(const int64_t *tile_offsets, int64_t n_tiles, int64_t t,
+                      int64_t i) {
+    while (t + 1 < n_tiles && tile_offsets[t + 1] <= i) t++;
+    return t;
 }
 
 DEV uint64_t ukey(int64_t k) { return (uint64_t)k ^ 0x8000000000000000ull; }
@@ -323,18 +395,13 @@ DEV int useq_cmp(const DevCol *cols, const uint8_t *col_dtype, int n_cols,
         const int c = ucols[j];
         const DevCol &a = cols[runA * n_cols + c];
         const DevCol &b = cols[runB * n_cols + c];
-        const uint8_t va =
-            a.valid0 ? ((const uint8_t *)a.valid0)[rowA] : 1;
-        const uint8_t vb =
-            b.valid0 ? ((const uint8_t *)b.valid0)[rowB] : 1;
+        const uint8_t va = col_valid(a, rowA);
+        const uint8_t vb = col_valid(b, rowB);
         if (va != vb) return va ? 1 : -1;  // null sorts first
         if (!va) continue;
         const int dt = col_dtype[c];
-        const bool wide = dt == 4 || dt == 6;
-        const int64_t x = wide ? col_load<int64_t>(a, rowA)
-                               : (int64_t)col_load<int32_t>(a, rowA);
-        const int64_t y = wide ? col_load<int64_t>(b, rowB)
-                               : (int64_t)col_load<int32_t>(b, rowB);
+        const int64_t x = col_load_wide(a, rowA, dt);
+        const int64_t y = col_load_wide(b, rowB, dt);
         if (x != y) return x > y ? 1 : -1;
     }
     return 0;
@@ -1750,8 +1817,7 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             }
         };
         auto stage_write = [&](int c, const int64_t *regs, uint8_t *slab) {
-            const int dt = col_dtype[c];
-            const bool wide = dt == 4 || dt == 6;
+            const bool wide = dt_wide(col_dtype[c]);
 #pragma unroll
             for (int s = 0; s < RMAX; s++) {
                 if (smap[s] == ~0u) continue;
@@ -1767,19 +1833,14 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
             for (int s = 0; s < RMAX; s++) {
                 if (smap[s] == ~0u) continue;
                 int32_t e = tid + s * PMH_TILE_THREADS;
-                const DevCol &dc =
-                    cols[(smap[s] >> PMH_ROW_BITS) * n_cols + c];
-                slab[e] = dc.valid0
-                    ? reinterpret_cast<const uint8_t *>(
-                          dc.valid0)[smap[s] & PMH_ROW_MASK]
-                    : 1;
+                slab[e] = member_valid(cols, n_cols, smap[s], c);
             }
         };
         auto emit_col = [&](int c, const uint8_t *slab,
                             const uint8_t *vslab) {
             if (ablate == 3) return;  // profiling: staging without emission
             const int dt = col_dtype[c];
-            const bool wide = dt == 4 || dt == 6;
+            const bool wide = dt_wide(dt);
             uint8_t *ov = (col_nullable[c] && out_valid[c]) ? out_valid[c]
                                                             : nullptr;
             for (int32_t i = tid; i < C; i += blockDim.x) {
@@ -1787,16 +1848,7 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 int64_t v = wide
                     ? reinterpret_cast<const int64_t *>(slab)[s]
                     : (int64_t)reinterpret_cast<const int32_t *>(slab)[s];
-                switch (dt) {
-                case 1: ((int8_t *)out_ptrs[c])[goff + i] = (int8_t)v; break;
-                case 2: ((int16_t *)out_ptrs[c])[goff + i] =
-                            (int16_t)v; break;
-                case 3:
-                case 5:
-                case 7: ((int32_t *)out_ptrs[c])[goff + i] =
-                            (int32_t)v; break;
-                default: ((int64_t *)out_ptrs[c])[goff + i] = v; break;
-                }
+                out_store(out_ptrs[c], dt, goff + i, v);
                 if (ov) ov[goff + i] = vslab ? vslab[s] : 1;
             }
         };
@@ -1826,16 +1878,7 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
         if (key_col >= 0) {
             const int kdt = col_dtype[key_col];
             for (int32_t i = tid; i < C; i += blockDim.x) {
-                int64_t v = key_of(wl[i]);
-                switch (kdt) {
-                case 1: ((int8_t *)out_ptrs[key_col])[goff + i] =
-                            (int8_t)v; break;
-                case 2: ((int16_t *)out_ptrs[key_col])[goff + i] =
-                            (int16_t)v; break;
-                case 3: ((int32_t *)out_ptrs[key_col])[goff + i] =
-                            (int32_t)v; break;
-                default: ((int64_t *)out_ptrs[key_col])[goff + i] = v; break;
-                }
+                out_store(out_ptrs[key_col], kdt, goff + i, key_of(wl[i]));
             }
         }
         for (int32_t i = tid; i < C; i += blockDim.x) {
@@ -1902,18 +1945,14 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     if (ov) {
                         uint8_t vv[R];
 #pragma unroll
-                        for (int x = 0; x < R; x++) {
-                            const DevCol &dc = cols[run[x] * n_cols + c];
-                            vv[x] = dc.valid0
-                                ? reinterpret_cast<const uint8_t *>(
-                                      dc.valid0)[row[x]]
-                                : 1;
-                        }
+                        for (int x = 0; x < R; x++)
+                            vv[x] = col_valid(cols[run[x] * n_cols + c],
+                                              row[x]);
 #pragma unroll
                         for (int x = 0; x < R; x++)
                             if (x < nr) ov[goff + idx[x]] = vv[x];
                     }
-                    if (dt == 4 || dt == 6) {
+                    if (dt_wide(dt)) {
                         int64_t v[R];
 #pragma unroll
                         for (int x = 0; x < R; x++)
@@ -1934,10 +1973,14 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                         for (int x = 0; x < R; x++) {
                             if (x >= nr) continue;
                             switch (dt) {
-                            case 1: ((int8_t *)out_ptrs[c])[goff + idx[x]] =
-                                        (int8_t)v[x]; break;
-                            case 2: ((int16_t *)out_ptrs[c])[goff + idx[x]] =
-                                        (int16_t)v[x]; break;
+                            case PMH_DT_INT8:
+                                ((int8_t *)out_ptrs[c])[goff + idx[x]] =
+                                    (int8_t)v[x];
+                                break;
+                            case PMH_DT_INT16:
+                                ((int16_t *)out_ptrs[c])[goff + idx[x]] =
+                                    (int16_t)v[x];
+                                break;
                             default: ((int32_t *)out_ptrs[c])[goff + idx[x]] =
                                         v[x]; break;
                             }
@@ -2004,12 +2047,8 @@ __global__ void k_emit_dense(const DevCol *cols, const uint8_t *col_dtype,
     const int64_t lo =
         t0 > 0 ? (int64_t)(status[t0 - 1] & LOOK_VAL) : 0;
     const int64_t total = (int64_t)(status[t1 - 1] & LOOK_VAL);
-    const int64_t span = total - lo;
-    const int64_t per_block =
-        (span + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = lo + (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi =
-        slice_lo + per_block < total ? slice_lo + per_block : total;
+    const int64_t slice_lo = lo + slice_lo_of(total - lo);
+    const int64_t slice_hi = lo + slice_hi_of(total - lo);
     for (int64_t base = slice_lo; base < slice_hi;
          base += (int64_t)blockDim.x * R) {
         int64_t i0 = base + threadIdx.x;
@@ -2038,18 +2077,13 @@ __global__ void k_emit_dense(const DevCol *cols, const uint8_t *col_dtype,
             if (col_nullable[c] && out_valid[c]) {
                 uint8_t vv[R];
 #pragma unroll
-                for (int x = 0; x < R; x++) {
-                    const DevCol &dc = cols[run[x] * n_cols + c];
-                    vv[x] = dc.valid0
-                        ? reinterpret_cast<const uint8_t *>(
-                              dc.valid0)[row[x]]
-                        : 1;
-                }
+                for (int x = 0; x < R; x++)
+                    vv[x] = col_valid(cols[run[x] * n_cols + c], row[x]);
 #pragma unroll
                 for (int x = 0; x < R; x++)
                     if (x < nr) out_valid[c][idx[x]] = vv[x];
             }
-            if (dt == 4 || dt == 6) {
+            if (dt_wide(dt)) {
                 int64_t v[R];
 #pragma unroll
                 for (int x = 0; x < R; x++)
@@ -2068,10 +2102,12 @@ __global__ void k_emit_dense(const DevCol *cols, const uint8_t *col_dtype,
                 for (int x = 0; x < R; x++) {
                     if (x >= nr) continue;
                     switch (dt) {
-                    case 1: ((int8_t *)out_ptrs[c])[idx[x]] =
-                                (int8_t)v[x]; break;
-                    case 2: ((int16_t *)out_ptrs[c])[idx[x]] =
-                                (int16_t)v[x]; break;
+                    case PMH_DT_INT8:
+                        ((int8_t *)out_ptrs[c])[idx[x]] = (int8_t)v[x];
+                        break;
+                    case PMH_DT_INT16:
+                        ((int16_t *)out_ptrs[c])[idx[x]] = (int16_t)v[x];
+                        break;
                     default: ((int32_t *)out_ptrs[c])[idx[x]] =
                                  v[x]; break;
                     }
@@ -2147,11 +2183,8 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
     // few tiles' source segments (~130 KB working set -> XCD-L2 resident;
     // grid-striding spread every block over the whole output and thrashed L2).
     const int64_t total = *total_out;
-    const int64_t per_block =
-        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi = slice_lo + per_block < total
-                                 ? slice_lo + per_block : total;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
     // one tile binary search per thread; ranks then advance monotonically
     // within the slice, so the tile cursor just walks forward. The R rows
     // per thread are WAVE-STRIDED (i = base + tid + x*blockDim), so every
@@ -2162,18 +2195,11 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
          base += (int64_t)blockDim.x * R) {
         int64_t i_first = base + threadIdx.x;
         if (i_first >= slice_hi) break;
-        if (t < 0) {  // first iteration: locate owning tile
-            int64_t lo = 0, hi = n_tiles - 1;
-            while (lo < hi) {
-                int64_t mid = (lo + hi + 1) >> 1;
-                if (tile_offsets[mid] <= i_first) lo = mid;
-                else hi = mid - 1;
-            }
-            t = lo;
-        }
+        // first iteration: locate owning tile
+        if (t < 0) t = tile_seek(tile_offsets, n_tiles, i_first);
         int64_t idx[R];
         int run[R];
-        int64_t row[R];
+        uint32_t row[R];
         int nr = 0;
 #pragma unroll
         for (int x = 0; x < R; x++) {
@@ -2183,7 +2209,7 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
             if (live) {
                 nr = x + 1;
                 // dense ranks: advance tile while i falls past its count
-                while (t + 1 < n_tiles && tile_offsets[t + 1] <= i) t++;
+                t = tile_walk(tile_offsets, n_tiles, t, i);
                 uint32_t packed =
                     winners[t * (tile_rows + PMH_MAX_RUNS) +
                             (i - tile_offsets[t])];
@@ -2200,13 +2226,12 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
 #pragma unroll
                 for (int x = 0; x < R; x++) {
                     if (x >= nr) continue;
-                    const DevCol &dc = cols[run[x] * n_cols + c];
                     out_valid[c][idx[x]] =
-                        dc.valid0 ? ((const uint8_t *)dc.valid0)[row[x]] : 1;
+                        col_valid(cols[run[x] * n_cols + c], row[x]);
                 }
             }
             switch (col_dtype[c]) {
-            case 1: {  // INT8 output from INT32-stored parquet TINYINT
+            case PMH_DT_INT8: {  // from INT32-stored parquet TINYINT
                 int32_t v[R];
 #pragma unroll
                 for (int x = 0; x < R; x++)
@@ -2217,7 +2242,7 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
                         ((int8_t *)out_ptrs[c])[idx[x]] = (int8_t)v[x];
                 break;
             }
-            case 2: {  // INT16 output from INT32-stored parquet SMALLINT
+            case PMH_DT_INT16: {  // from INT32-stored parquet SMALLINT
                 int32_t v[R];
 #pragma unroll
                 for (int x = 0; x < R; x++)
@@ -2228,9 +2253,9 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
                         ((int16_t *)out_ptrs[c])[idx[x]] = (int16_t)v[x];
                 break;
             }
-            case 3:
-            case 5:
-            case 7: {  // string ids ride as int32
+            case PMH_DT_INT32:
+            case PMH_DT_FLOAT32:
+            case PMH_DT_STRING: {  // string ids ride as int32
                 int32_t v[R];
 #pragma unroll
                 for (int x = 0; x < R; x++)
@@ -2240,8 +2265,8 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
                     if (x < nr) ((int32_t *)out_ptrs[c])[idx[x]] = v[x];
                 break;
             }
-            case 4:
-            case 6: {
+            case PMH_DT_INT64:
+            case PMH_DT_FLOAT64: {
                 int64_t v[R];
 #pragma unroll
                 for (int x = 0; x < R; x++)
@@ -2259,14 +2284,13 @@ __global__ void k_emit(const DevCol *cols /* n_runs * n_cols, run-major */,
 
 // ------------------------------------------------------ k_emit_contig
 //
-// k_emit for plans whose columns are all contiguous (n_pages == 1 in every
-// descriptor, which is every plan built today). Same work division: a
-// contiguous output slice per block, wave-strided rows, dead lanes repeat
-// row 0's gather with their stores guarded. What differs is that nothing
-// inside the row / column loops depends on a descriptor read from global
-// memory -- k_emit paid three dependent round trips per row and column
-// (n_pages, addr0, data), with every wait a full drain, so its R "parallel"
-// gathers ran one after another (profiles/emit_phases.md):
+// k_emit with its descriptors in LDS, for plans whose tables fit. Same work
+// division: a contiguous output slice per block, wave-strided rows, dead lanes
+// repeat row 0's gather with their stores guarded. What differs is that
+// nothing inside the row / column loops depends on a descriptor read from
+// global memory -- k_emit pays dependent round trips per row and column
+// (descriptor, then data), with every wait a full drain, so its R "parallel"
+// gathers run one after another (profiles/emit_phases.md):
 //  * addr0 / valid0 of the n_desc runs the winners can name, and per column
 //    {list position, output pointer, validity output pointer}, are staged in
 //    LDS once per block; a gather address is one LDS read + row * width;
@@ -2407,36 +2431,17 @@ void k_emit_contig(const DevCol *cols /* n_desc * n_cols, run-major */,
 
     const int tid = threadIdx.x;
     const int64_t total = *total_out;
-    const int64_t per_block =
-        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi = slice_lo + per_block < total
-                                 ? slice_lo + per_block : total;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
     if (slice_lo >= slice_hi) return;  // block-uniform, before any barrier
 
-    // a column's list = the width its output is stored at, by dtype as in
-    // k_emit's switch (1 / 2 narrow INT32-stored TINYINT / SMALLINT; 5 / 6 /
-    // 7 move as raw 32 / 64 / 32-bit words); 0 = not emitted
-    auto dt_class = [](int dt) {
-        return dt == 1 ? 1
-               : dt == 2 ? 2
-               : (dt == 3 || dt == 5 || dt == 7) ? 4
-               : (dt == 4 || dt == 6) ? 8
-                                      : 0;
-    };
+    // a column's list = the width its output is stored at (TINYINT / SMALLINT
+    // narrow from their INT32-stored values; floats and string ids move as
+    // raw words); 0 = not emitted
     for (int c = tid; c < n_cols; c += EMIT_THREADS)
-        s_cls[c] = c < n_emit ? dt_class(col_dtype[c]) : 0;
+        s_cls[c] = c < n_emit ? pmh_out_width(col_dtype[c]) : 0;
     // the tile that owns slice_lo (block-uniform search, every thread)
-    int64_t t0;
-    {
-        int64_t lo = 0, hi = n_tiles - 1;
-        while (lo < hi) {
-            int64_t mid = (lo + hi + 1) >> 1;
-            if (tile_offsets[mid] <= slice_lo) lo = mid;
-            else hi = mid - 1;
-        }
-        t0 = lo;
-    }
+    const int64_t t0 = tile_seek(tile_offsets, n_tiles, slice_lo);
     for (int j = tid; j <= EMIT_WIN; j += EMIT_THREADS)
         s_toff[j] = t0 + j < n_tiles ? tile_offsets[t0 + j] : INT64_MAX;
     __syncthreads();
@@ -2693,15 +2698,8 @@ void k_emit_stream(const DevCol *cols /* k * n_cols, run-major */,
 
     const int tid = threadIdx.x;
     // the lists, as in k_emit_contig
-    auto dt_class = [](int dt) {
-        return dt == 1 ? 1
-               : dt == 2 ? 2
-               : (dt == 3 || dt == 5 || dt == 7) ? 4
-               : (dt == 4 || dt == 6) ? 8
-                                      : 0;
-    };
     for (int c = tid; c < n_cols; c += EMS_THREADS)
-        s_cls[c] = c < n_emit ? dt_class(col_dtype[c]) : 0;
+        s_cls[c] = c < n_emit ? pmh_out_width(col_dtype[c]) : 0;
     __syncthreads();
     for (int c = tid; c < n_cols; c += EMS_THREADS) {
         const int cls = s_cls[c];
@@ -2872,9 +2870,7 @@ __global__ void k_pack_valid(const DevCol *cols, int n_cols, int64_t rows,
          i += stride) {
         uint64_t m = 0;
         for (int c = 0; c < n_cols; c++) {
-            const DevCol &dc = cols[c];
-            uint64_t v =
-                dc.valid0 ? (uint64_t)((const uint8_t *)dc.valid0)[i] : 1u;
+            const uint64_t v = col_valid(cols[c], i);
             m |= (v & 1) << c;
         }
         mask[i] = m;
@@ -2911,24 +2907,22 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
     // DELETE were already dropped by the merge pass under drop_delete.
     const bool rrod = (flags & 16) != 0;
     const int64_t total = *total_out;
-    const int64_t per_block =
-        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi =
-        slice_lo + per_block < total ? slice_lo + per_block : total;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
+    auto kind_of = [&](uint32_t m) -> int32_t {
+        return col_load<int32_t>(member_col(cols, n_cols, m, kind_col),
+                                 member_row(m));
+    };
+    auto valid_of = [&](uint32_t m, int c) -> uint8_t {
+        if (MASKS) return (uint8_t)((member_mask(run_masks, m) >> c) & 1);
+        return member_valid(cols, n_cols, m, c);
+    };
     int64_t t = -1;
     for (int64_t i = slice_lo + threadIdx.x; i < slice_hi; i += blockDim.x) {
-        if (t < 0) {  // first iteration: binary-search the owning tile; i
-                      // then grows monotonically, so a forward cursor walks
-            int64_t lo = 0, hi = n_tiles - 1;
-            while (lo < hi) {
-                int64_t mid = (lo + hi + 1) >> 1;
-                if (tile_offsets[mid] <= i) lo = mid;
-                else hi = mid - 1;
-            }
-            t = lo;
-        }
-        while (t + 1 < n_tiles && tile_offsets[t + 1] <= i) t++;
+        // first iteration: binary-search the owning tile; i then grows
+        // monotonically, so a forward cursor walks
+        if (t < 0) t = tile_seek(tile_offsets, n_tiles, i);
+        t = tile_walk(tile_offsets, n_tiles, t, i);
         int64_t g = i - tile_offsets[t];
         const uint16_t *gs = &group_start[t * (tile_rows + 1)];
         const uint32_t *mem = &members[t * (tile_rows + PMH_MAX_RUNS)];
@@ -2946,21 +2940,19 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
         if (MASKS) {
 #pragma unroll
             for (int x = 0; x < 4; x++)
-                vm[x] = x < gn
-                            ? run_masks[mc[x] >> PMH_ROW_BITS][mc[x] & PMH_ROW_MASK]
-                            : 0;
+                vm[x] = x < gn ? member_mask(run_masks, mc[x]) : 0;
         }
-        uint32_t last = mc[0];
-        int lrun = last >> PMH_ROW_BITS;
-        int64_t lrow = last & PMH_ROW_MASK;
+        // validity of cached member x: from its cached mask where there is one
+        auto valid_cached = [&](int x, int c) -> uint8_t {
+            return MASKS ? (uint8_t)((vm[x] >> c) & 1) : valid_of(mc[x], c);
+        };
+        const uint32_t last = mc[0];
         // singleton bypass serves the record's own RowKind: issue that
         // gather HERE so it overlaps the member prefetch instead of
         // stalling the column loop (measured +65% on emit_pu when loaded
         // at the kind column)
         int32_t single_kind = 0;
-        if (gn == 1)
-            single_kind = col_load<int32_t>(
-                cols[lrun * n_cols + kind_col], lrow);
+        if (gn == 1) single_kind = kind_of(last);
         // newest-first index of the last DELETE member; gn = none (also the
         // value when RROD is off, which neutralizes every bound below)
         int j_del = gn;
@@ -2968,14 +2960,10 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
 #pragma unroll
             for (int x = 0; x < 4; x++) {
                 if (x >= gn || j_del < gn) continue;
-                const DevCol &dc = cols[(mc[x] >> PMH_ROW_BITS) * n_cols + kind_col];
-                if (col_load<int32_t>(dc, mc[x] & PMH_ROW_MASK) == 3) j_del = x;
+                if (kind_of(mc[x]) == 3) j_del = x;
             }
-            for (int x = 4; x < gn && j_del == gn; x++) {
-                uint32_t m = mem[me - 1 - x];
-                const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + kind_col];
-                if (col_load<int32_t>(dc, m & PMH_ROW_MASK) == 3) j_del = x;
-            }
+            for (int x = 4; x < gn && j_del == gn; x++)
+                if (kind_of(mem[me - 1 - x]) == 3) j_del = x;
         }
         for (int c = 0; c < n_cols; c++) {
             if (c == kind_col) {
@@ -2985,100 +2973,42 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
                             : ((rrod && j_del == 0) ? 3 : 0));
                 continue;
             }
-            int64_t run = lrun, row = lrow;
+            uint32_t src = last;  // the member whose field is emitted
             uint8_t ok = 1;
             if (col_nullable[c] && gn > 1) {
                 ok = 0;
 #pragma unroll
                 for (int x = 0; x < 4; x++) {
                     if (ok || x >= gn || x >= j_del) continue;
-                    uint32_t m = mc[x];
-                    uint8_t v;
-                    if (MASKS) {
-                        v = (uint8_t)((vm[x] >> c) & 1);
-                    } else {
-                        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-                        v = dc.valid0
-                                ? ((const uint8_t *)dc.valid0)[m & PMH_ROW_MASK]
-                                : 1;
-                    }
-                    if (v) {
-                        run = m >> PMH_ROW_BITS;
-                        row = m & PMH_ROW_MASK;
+                    if (valid_cached(x, c)) {
+                        src = mc[x];
                         ok = 1;
                     }
                 }
                 for (int32_t x = me - 5; !ok && x >= ms; x--) {
                     if (me - 1 - x >= j_del) break;  // not newer than DELETE
-                    uint32_t m = mem[x];
-                    uint8_t v;
-                    if (MASKS) {
-                        v = (uint8_t)(
-                            (run_masks[m >> PMH_ROW_BITS][m & PMH_ROW_MASK] >> c) & 1);
-                    } else {
-                        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-                        v = dc.valid0
-                                ? ((const uint8_t *)dc.valid0)[m & PMH_ROW_MASK]
-                                : 1;
-                    }
-                    if (v) {
-                        run = m >> PMH_ROW_BITS;
-                        row = m & PMH_ROW_MASK;
+                    const uint32_t m = mem[x];
+                    if (valid_of(m, c)) {
+                        src = m;
                         ok = 1;
                     }
                 }
             } else if (col_nullable[c]) {
                 // singleton: the record passes through with its own validity
-                if (MASKS) {
-                    ok = (uint8_t)((vm[0] >> c) & 1);
-                } else {
-                    const DevCol &dc = cols[lrun * n_cols + c];
-                    ok = dc.valid0 ? ((const uint8_t *)dc.valid0)[lrow] : 1;
-                }
+                ok = valid_cached(0, c);
             }
             if (!ok && j_del < gn && col_nullable[c] && gn > 1) {
                 // no add newer than the DELETE set this field: the row was
                 // re-initialized from the DELETE record's value (initRow)
-                uint32_t m = mem[me - 1 - j_del];
-                uint8_t v;
-                if (MASKS) {
-                    v = (uint8_t)(
-                        (run_masks[m >> PMH_ROW_BITS][m & PMH_ROW_MASK] >> c) & 1);
-                } else {
-                    const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-                    v = dc.valid0
-                            ? ((const uint8_t *)dc.valid0)[m & PMH_ROW_MASK]
-                            : 1;
-                }
-                if (v) {
-                    run = m >> PMH_ROW_BITS;
-                    row = m & PMH_ROW_MASK;
+                const uint32_t m = mem[me - 1 - j_del];
+                if (valid_of(m, c)) {
+                    src = m;
                     ok = 1;
                 }
             }
-            const DevCol &dc = cols[run * n_cols + c];
-            switch (col_dtype[c]) {
-            case 1:
-                ((int8_t *)out_ptrs[c])[i] =
-                    ok ? (int8_t)col_load<int32_t>(dc, row) : 0;
-                break;
-            case 2:
-                ((int16_t *)out_ptrs[c])[i] =
-                    ok ? (int16_t)col_load<int32_t>(dc, row) : 0;
-                break;
-            case 3:
-            case 5:
-            case 7:  // string ids ride as int32
-                ((int32_t *)out_ptrs[c])[i] =
-                    ok ? col_load<int32_t>(dc, row) : 0;
-                break;
-            case 4:
-            case 6:
-                ((int64_t *)out_ptrs[c])[i] =
-                    ok ? col_load<int64_t>(dc, row) : 0;
-                break;
-            default: break;
-            }
+            const int dt = col_dtype[c];
+            out_store(out_ptrs[c], dt, i,
+                      ok ? member_load(cols, n_cols, src, c, dt) : 0);
             if (out_valid[c]) out_valid[c][i] = ok;
         }
     }
@@ -3117,43 +3047,23 @@ __global__ void k_emit_pu_sg(const DevCol *cols, const uint8_t *col_dtype,
                              uint8_t *const *out_valid) {
     const bool ignore_delete = flags & 2;
     const int64_t total = *total_out;
-    const int64_t per_block =
-        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi =
-        slice_lo + per_block < total ? slice_lo + per_block : total;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
     auto kind_of = [&](uint32_t m) -> int32_t {
-        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + kind_col];
-        return col_load<int32_t>(dc, m & PMH_ROW_MASK);
+        return col_load<int32_t>(member_col(cols, n_cols, m, kind_col),
+                                 member_row(m));
     };
     auto valid_of = [&](uint32_t m, int c) -> uint8_t {
-        if (run_masks)
-            return (uint8_t)(
-                (run_masks[m >> PMH_ROW_BITS][m & PMH_ROW_MASK] >> c) & 1);
-        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-        return dc.valid0
-                   ? ((const uint8_t *)dc.valid0)[m & PMH_ROW_MASK]
-                   : 1;
+        if (run_masks) return (uint8_t)((member_mask(run_masks, m) >> c) & 1);
+        return member_valid(cols, n_cols, m, c);
     };
     auto load_of = [&](uint32_t m, int c) -> int64_t {
-        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-        const int dt = col_dtype[c];
-        return (dt == 4 || dt == 6)
-                   ? col_load<int64_t>(dc, m & PMH_ROW_MASK)
-                   : (int64_t)col_load<int32_t>(dc, m & PMH_ROW_MASK);
+        return member_load(cols, n_cols, m, c, col_dtype[c]);
     };
     int64_t t = -1;
     for (int64_t i = slice_lo + threadIdx.x; i < slice_hi; i += blockDim.x) {
-        if (t < 0) {
-            int64_t lo = 0, hi = n_tiles - 1;
-            while (lo < hi) {
-                int64_t mid = (lo + hi + 1) >> 1;
-                if (tile_offsets[mid] <= i) lo = mid;
-                else hi = mid - 1;
-            }
-            t = lo;
-        }
-        while (t + 1 < n_tiles && tile_offsets[t + 1] <= i) t++;
+        if (t < 0) t = tile_seek(tile_offsets, n_tiles, i);
+        t = tile_walk(tile_offsets, n_tiles, t, i);
         const int64_t g = i - tile_offsets[t];
         const uint16_t *gs = &group_start[t * (tile_rows + 1)];
         const uint32_t *mem = &members[t * (tile_rows + PMH_MAX_RUNS)];
@@ -3171,15 +3081,8 @@ __global__ void k_emit_pu_sg(const DevCol *cols, const uint8_t *col_dtype,
                     continue;
                 }
                 uint8_t ok = col_nullable[c] ? valid_of(m0, c) : 1;
-                const int64_t v = ok ? load_of(m0, c) : 0;
-                switch (col_dtype[c]) {
-                case 1: ((int8_t *)out_ptrs[c])[i] = (int8_t)v; break;
-                case 2: ((int16_t *)out_ptrs[c])[i] = (int16_t)v; break;
-                case 3:
-                case 5:
-                case 7: ((int32_t *)out_ptrs[c])[i] = (int32_t)v; break;
-                default: ((int64_t *)out_ptrs[c])[i] = v; break;
-                }
+                out_store(out_ptrs[c], col_dtype[c], i,
+                          ok ? load_of(m0, c) : 0);
                 if (out_valid[c]) out_valid[c][i] = ok;
             }
             continue;
@@ -3284,16 +3187,8 @@ __global__ void k_emit_pu_sg(const DevCol *cols, const uint8_t *col_dtype,
                     }
                 }
             }
-            const int dt = col_dtype[c];
-            const int64_t v = ok ? load_of(src_m, c) : 0;
-            switch (dt) {
-            case 1: ((int8_t *)out_ptrs[c])[i] = (int8_t)v; break;
-            case 2: ((int16_t *)out_ptrs[c])[i] = (int16_t)v; break;
-            case 3:
-            case 5:
-            case 7: ((int32_t *)out_ptrs[c])[i] = (int32_t)v; break;
-            default: ((int64_t *)out_ptrs[c])[i] = v; break;
-            }
+            out_store(out_ptrs[c], col_dtype[c], i,
+                      ok ? load_of(src_m, c) : 0);
             if (out_valid[c]) out_valid[c][i] = ok;
         }
     }
@@ -3341,31 +3236,23 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
     // with the last DELETE's field and consume only newer adds. first_*
     // aggregators are rejected at plan creation under this mode.
     const bool rrod = (flags & 16) != 0;
+    auto kind_of = [&](uint32_t m) -> int32_t {
+        return col_load<int32_t>(member_col(cols, n_cols, m, kind_col),
+                                 member_row(m));
+    };
     auto valid_of = [&](uint32_t m, int c) -> uint8_t {
-        if (MASKS)
-            return (uint8_t)((run_masks[m >> PMH_ROW_BITS][m & PMH_ROW_MASK] >> c) & 1);
-        const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-        return dc.valid0 ? ((const uint8_t *)dc.valid0)[m & PMH_ROW_MASK] : 1;
+        if (MASKS) return (uint8_t)((member_mask(run_masks, m) >> c) & 1);
+        return member_valid(cols, n_cols, m, c);
     };
     const int64_t total = *total_out;
-    const int64_t per_block =
-        (total + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
-    const int64_t slice_lo = (int64_t)blockIdx.x * per_block;
-    const int64_t slice_hi =
-        slice_lo + per_block < total ? slice_lo + per_block : total;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
     int64_t t = -1;
     for (int64_t i = slice_lo + threadIdx.x; i < slice_hi; i += blockDim.x) {
-        if (t < 0) {  // first iteration: binary-search the owning tile; i
-                      // then grows monotonically, so a forward cursor walks
-            int64_t lo = 0, hi = n_tiles - 1;
-            while (lo < hi) {
-                int64_t mid = (lo + hi + 1) >> 1;
-                if (tile_offsets[mid] <= i) lo = mid;
-                else hi = mid - 1;
-            }
-            t = lo;
-        }
-        while (t + 1 < n_tiles && tile_offsets[t + 1] <= i) t++;
+        // first iteration: binary-search the owning tile; i then grows
+        // monotonically, so a forward cursor walks
+        if (t < 0) t = tile_seek(tile_offsets, n_tiles, i);
+        t = tile_walk(tile_offsets, n_tiles, t, i);
         int64_t g = i - tile_offsets[t];
         const uint16_t *gs = &group_start[t * (tile_rows + 1)];
         const uint32_t *mem = &members[t * (tile_rows + PMH_MAX_RUNS)];
@@ -3383,10 +3270,12 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
         if (MASKS) {
 #pragma unroll
             for (int x = 0; x < 4; x++)
-                vma[x] = x < gn
-                             ? run_masks[ma[x] >> PMH_ROW_BITS][ma[x] & PMH_ROW_MASK]
-                             : 0;
+                vma[x] = x < gn ? member_mask(run_masks, ma[x]) : 0;
         }
+        // validity of cached member x: from its cached mask where there is one
+        auto valid_cached = [&](int x, int c) -> uint8_t {
+            return MASKS ? (uint8_t)((vma[x] >> c) & 1) : valid_of(ma[x], c);
+        };
         uint32_t last = ma[0];
         uint64_t vlast = MASKS ? vma[0] : 0;
 #pragma unroll
@@ -3397,15 +3286,11 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
             }
         if (gn > 4) {
             last = mem[me - 1];
-            if (MASKS) vlast = run_masks[last >> PMH_ROW_BITS][last & PMH_ROW_MASK];
+            if (MASKS) vlast = member_mask(run_masks, last);
         }
-        const int lrun = last >> PMH_ROW_BITS;
-        const int64_t lrow = last & PMH_ROW_MASK;
         // singleton bypass kind, issued early to overlap (see k_emit_pu)
         int32_t single_kind = 0;
-        if (gn == 1)
-            single_kind = col_load<int32_t>(
-                cols[lrun * n_cols + kind_col], lrow);
+        if (gn == 1) single_kind = kind_of(last);
         // ascending index of the LAST DELETE member (-1 = none)
         int d_del = -1;
         uint32_t mdel = 0;
@@ -3414,17 +3299,13 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
 #pragma unroll
             for (int x = 0; x < 4; x++) {
                 if (x >= gn) continue;
-                const DevCol &dc = cols[(ma[x] >> PMH_ROW_BITS) * n_cols + kind_col];
-                if (col_load<int32_t>(dc, ma[x] & PMH_ROW_MASK) == 3) d_del = x;
+                if (kind_of(ma[x]) == 3) d_del = x;
             }
-            for (int x = 4; x < gn; x++) {
-                uint32_t m = mem[ms + x];
-                const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + kind_col];
-                if (col_load<int32_t>(dc, m & PMH_ROW_MASK) == 3) d_del = x;
-            }
+            for (int x = 4; x < gn; x++)
+                if (kind_of(mem[ms + x]) == 3) d_del = x;
             if (d_del >= 0) {
                 mdel = mem[ms + d_del];
-                if (MASKS) vdel = run_masks[mdel >> PMH_ROW_BITS][mdel & PMH_ROW_MASK];
+                if (MASKS) vdel = member_mask(run_masks, mdel);
             }
         }
         // retract mode (flags bit 64): per-member kinds drive
@@ -3450,15 +3331,12 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
             auto del_valid = [&]() -> uint8_t {
                 if (!col_nullable[c]) return 1;
                 if (MASKS) return (uint8_t)((vdel >> c) & 1);
-                const DevCol &dc = cols[(mdel >> PMH_ROW_BITS) * n_cols + c];
-                return dc.valid0
-                           ? ((const uint8_t *)dc.valid0)[mdel & PMH_ROW_MASK]
-                           : 1;
+                return member_valid(cols, n_cols, mdel, c);
             };
-            int64_t run = lrun, row = lrow;
+            uint32_t src = last;  // the member whose field is emitted
             uint8_t ok = 1;
             int64_t bits = 0;  // result payload (raw stored bits / int value)
-            bool direct = true;  // bits not set; load from (run,row) at store
+            bool direct = true;  // bits not set; load from src at store
             bool handled = false;
             if (aggr && ign_retract && gn > 1 &&
                 (agg == PMH_AGG_LAST_VALUE || agg == PMH_AGG_FIRST_VALUE ||
@@ -3467,10 +3345,7 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                 // FieldIgnoreRetractAgg wrapper: retract members leave the
                 // accumulator untouched, so only ADD members qualify
                 auto is_rt = [&](uint32_t m) -> bool {
-                    const DevCol &dc =
-                        cols[(m >> PMH_ROW_BITS) * n_cols + kind_col];
-                    const int32_t kd =
-                        col_load<int32_t>(dc, m & PMH_ROW_MASK);
+                    const int32_t kd = kind_of(m);
                     return kd == 1 || kd == 3;
                 };
                 const bool want_first = agg == PMH_AGG_FIRST_VALUE ||
@@ -3483,8 +3358,7 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                     if (is_rt(m)) continue;
                     uint8_t v = col_nullable[c] ? valid_of(m, c) : 1;
                     if (need_nn && !v) continue;
-                    run = m >> PMH_ROW_BITS;
-                    row = m & PMH_ROW_MASK;
+                    src = m;
                     ok = need_nn ? 1 : v;
                     if (want_first) break;
                 }
@@ -3499,11 +3373,9 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                                : valid_of(last, c);
                 break;
             case PMH_AGG_FIRST_VALUE: {
-                run = ma[0] >> PMH_ROW_BITS;
-                row = ma[0] & PMH_ROW_MASK;
+                src = ma[0];
                 if (col_nullable[c])
-                    ok = MASKS ? (uint8_t)((vma[0] >> c) & 1)
-                               : valid_of(ma[0], c);
+                    ok = valid_cached(0, c);
                 break;
             }
             case PMH_AGG_LAST_NON_NULL:
@@ -3515,25 +3387,20 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                         if (x <= d_del) break;
                         uint32_t m = mem[ms + x];
                         if (valid_of(m, c)) {
-                            run = m >> PMH_ROW_BITS;
-                            row = m & PMH_ROW_MASK;
+                            src = m;
                             ok = 1;
                         }
                     }
 #pragma unroll
                     for (int x = 3; x >= 0; x--) {
                         if (ok || x >= gn || x <= d_del) continue;
-                        uint8_t v = MASKS ? (uint8_t)((vma[x] >> c) & 1)
-                                          : valid_of(ma[x], c);
-                        if (v) {
-                            run = ma[x] >> PMH_ROW_BITS;
-                            row = ma[x] & PMH_ROW_MASK;
+                        if (valid_cached(x, c)) {
+                            src = ma[x];
                             ok = 1;
                         }
                     }
                     if (!ok && d_del >= 0 && del_valid()) {
-                        run = mdel >> PMH_ROW_BITS;  // initRow: the DELETE's field
-                        row = mdel & PMH_ROW_MASK;
+                        src = mdel;  // initRow: the DELETE's field
                         ok = 1;
                     }
                 }
@@ -3544,25 +3411,20 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
 #pragma unroll
                     for (int x = 0; x < 4; x++) {
                         if (ok || x >= gn) continue;
-                        uint8_t v = MASKS ? (uint8_t)((vma[x] >> c) & 1)
-                                          : valid_of(ma[x], c);
-                        if (v) {
-                            run = ma[x] >> PMH_ROW_BITS;
-                            row = ma[x] & PMH_ROW_MASK;
+                        if (valid_cached(x, c)) {
+                            src = ma[x];
                             ok = 1;
                         }
                     }
                     for (int32_t x = 4; !ok && x < gn; x++) {
                         uint32_t m = mem[ms + x];
                         if (valid_of(m, c)) {
-                            run = m >> PMH_ROW_BITS;
-                            row = m & PMH_ROW_MASK;
+                            src = m;
                             ok = 1;
                         }
                     }
                 } else {
-                    run = ma[0] >> PMH_ROW_BITS;
-                    row = ma[0] & PMH_ROW_MASK;
+                    src = ma[0];
                 }
                 break;
             default: {  // SUM / MAX / MIN: full fold, null inputs skipped
@@ -3572,17 +3434,13 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                 float facc = 0.f;
                 double dacc = 0.0;
                 auto fold_one = [&](uint32_t m, bool retract) {
-                    const DevCol &dc = cols[(m >> PMH_ROW_BITS) * n_cols + c];
-                    const int64_t r = m & PMH_ROW_MASK;
-                    int64_t vb = (dt == 4 || dt == 6)
-                                     ? col_load<int64_t>(dc, r)
-                                     : (int64_t)col_load<int32_t>(dc, r);
+                    const int64_t vb = member_load(cols, n_cols, m, c, dt);
                     if (!ok) {
                         ok = 1;
-                        if (agg == PMH_AGG_SUM && dt == 5) {
+                        if (agg == PMH_AGG_SUM && dt == PMH_DT_FLOAT32) {
                             facc = __int_as_float((int32_t)vb);
                             if (retract) facc = -facc;  // null acc: negate
-                        } else if (agg == PMH_AGG_SUM && dt == 6) {
+                        } else if (agg == PMH_AGG_SUM && dt == PMH_DT_FLOAT64) {
                             dacc = __longlong_as_double(vb);
                             if (retract) dacc = -dacc;
                         } else {
@@ -3594,19 +3452,19 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                         // FieldSumAgg.agg / .retract (:60-110): subtract on
                         // retract, same width/precision rules
                         const double sgn = retract ? -1.0 : 1.0;
-                        if (dt == 5)
+                        if (dt == PMH_DT_FLOAT32)
                             facc += (float)sgn * __int_as_float((int32_t)vb);
-                        else if (dt == 6)
+                        else if (dt == PMH_DT_FLOAT64)
                             dacc += sgn * __longlong_as_double(vb);
                         else
                             iacc += retract ? -vb : vb;
                     } else {
                         bool take;
-                        if (dt == 5) {
+                        if (dt == PMH_DT_FLOAT32) {
                             uint32_t a = f32_ord((int32_t)iacc);
                             uint32_t b = f32_ord((int32_t)vb);
                             take = agg == PMH_AGG_MAX ? b > a : b < a;
-                        } else if (dt == 6) {
+                        } else if (dt == PMH_DT_FLOAT64) {
                             uint64_t a = f64_ord(iacc);
                             uint64_t b = f64_ord(vb);
                             take = agg == PMH_AGG_MAX ? b > a : b < a;
@@ -3618,10 +3476,7 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                 };
                 auto is_retract = [&](uint32_t m) -> bool {
                     if (!aggr) return false;
-                    const DevCol &dc =
-                        cols[(m >> PMH_ROW_BITS) * n_cols + kind_col];
-                    const int32_t kd =
-                        col_load<int32_t>(dc, m & PMH_ROW_MASK);
+                    const int32_t kd = kind_of(m);
                     return kd == 1 || kd == 3;
                 };
                 if (d_del >= 0 && del_valid())
@@ -3629,10 +3484,7 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
 #pragma unroll
                 for (int x = 0; x < 4; x++) {
                     if (x >= gn || x <= d_del) continue;
-                    if (col_nullable[c] &&
-                        !(MASKS ? (uint8_t)((vma[x] >> c) & 1)
-                                : valid_of(ma[x], c)))
-                        continue;
+                    if (col_nullable[c] && !valid_cached(x, c)) continue;
                     const bool rt = is_retract(ma[x]);
                     if (rt && ign_retract) continue;  // FieldIgnoreRetractAgg
                     fold_one(ma[x], rt);
@@ -3645,33 +3497,18 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                     if (rt && ign_retract) continue;
                     fold_one(m, rt);
                 }
-                if (agg == PMH_AGG_SUM && dt == 5)
+                if (agg == PMH_AGG_SUM && dt == PMH_DT_FLOAT32)
                     bits = (int64_t)__float_as_int(facc);
-                else if (agg == PMH_AGG_SUM && dt == 6)
+                else if (agg == PMH_AGG_SUM && dt == PMH_DT_FLOAT64)
                     bits = __double_as_longlong(dacc);
                 else
                     bits = iacc;
                 break;
             }
             }
-            if (direct) {
-                const DevCol &dc = cols[run * n_cols + c];
-                if (ok)
-                    bits = (dt == 4 || dt == 6)
-                               ? col_load<int64_t>(dc, row)
-                               : (int64_t)col_load<int32_t>(dc, row);
-            }
+            if (direct && ok) bits = member_load(cols, n_cols, src, c, dt);
             if (!ok) bits = 0;
-            switch (dt) {
-            case 1: ((int8_t *)out_ptrs[c])[i] = (int8_t)bits; break;
-            case 2: ((int16_t *)out_ptrs[c])[i] = (int16_t)bits; break;
-            case 3:
-            case 5:
-            case 7: ((int32_t *)out_ptrs[c])[i] = (int32_t)bits; break;
-            case 4:
-            case 6: ((int64_t *)out_ptrs[c])[i] = bits; break;
-            default: break;
-            }
+            out_store(out_ptrs[c], dt, i, bits);
             if (out_valid[c]) out_valid[c][i] = ok;
         }
     }
@@ -4323,8 +4160,7 @@ __global__ void k_filter(const DevCol *cols, int n_cols,
         for (int t = 0; t < n_terms && pass; t++) {
             const FilterTerm &ft = terms[t];
             const DevCol &dc = cols[ft.col];
-            bool valid =
-                !dc.valid0 || ((const uint8_t *)dc.valid0)[i] != 0;
+            bool valid = col_valid(dc, i) != 0;
             if (ft.op == 6) {
                 pass = !valid;
                 continue;
@@ -4443,18 +4279,13 @@ __global__ void k_cl_finalize(const DevCol *cols, const uint8_t *col_dtype,
             int nv = ((e0 >> 35) & 1) + ((e1 >> 35) & 1);
             if ((e0 >> 36) & 1) {  // pending pair: value-equality check
                 uint32_t a = (uint32_t)e0, b = (uint32_t)e1;
-                int ra = a >> PMH_ROW_BITS, rb = b >> PMH_ROW_BITS;
-                int64_t xa = a & PMH_ROW_MASK, xb = b & PMH_ROW_MASK;
+                int64_t xa = member_row(a), xb = member_row(b);
                 bool eq = true;
                 for (int c = first_val; eq && c < n_cols; c++) {
-                    const DevCol &da = cols[ra * n_cols + c];
-                    const DevCol &db = cols[rb * n_cols + c];
-                    uint8_t va = da.valid0
-                                     ? ((const uint8_t *)da.valid0)[xa]
-                                     : 1;
-                    uint8_t vb = db.valid0
-                                     ? ((const uint8_t *)db.valid0)[xb]
-                                     : 1;
+                    const DevCol &da = member_col(cols, n_cols, a, c);
+                    const DevCol &db = member_col(cols, n_cols, b, c);
+                    uint8_t va = col_valid(da, xa);
+                    uint8_t vb = col_valid(db, xb);
                     if (va != vb) {
                         eq = false;
                     } else if (va) {
@@ -4516,40 +4347,18 @@ __global__ void k_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
         for (int32_t i = threadIdx.x; i < n; i += blockDim.x) {
             uint64_t e = in[i];
             uint32_t m = (uint32_t)e;
-            int run = m >> PMH_ROW_BITS;
-            int64_t row = m & PMH_ROW_MASK;
             int8_t kd = (int8_t)((e >> 32) & 7);
             int64_t o = ob + i;
             for (int c = 0; c < n_cols; c++) {
-                const DevCol &dc = cols[run * n_cols + c];
                 if (col_nullable[c] && out_valid[c])
-                    out_valid[c][o] =
-                        dc.valid0 ? ((const uint8_t *)dc.valid0)[row] : 1;
+                    out_valid[c][o] = member_valid(cols, n_cols, m, c);
                 if (c == kind_col) {
                     ((int8_t *)out_ptrs[c])[o] = kd;
                     continue;
                 }
-                switch (col_dtype[c]) {
-                case 1:
-                    ((int8_t *)out_ptrs[c])[o] =
-                        (int8_t)col_load<int32_t>(dc, row);
-                    break;
-                case 2:
-                    ((int16_t *)out_ptrs[c])[o] =
-                        (int16_t)col_load<int32_t>(dc, row);
-                    break;
-                case 3:
-                case 5:
-                case 7:
-                    ((int32_t *)out_ptrs[c])[o] = col_load<int32_t>(dc, row);
-                    break;
-                case 4:
-                case 6:
-                    ((int64_t *)out_ptrs[c])[o] = col_load<int64_t>(dc, row);
-                    break;
-                default:
-                    break;
-                }
+                const int dt = col_dtype[c];
+                out_store(out_ptrs[c], dt, o,
+                          member_load(cols, n_cols, m, c, dt));
             }
         }
         __syncthreads();
@@ -4572,7 +4381,7 @@ __global__ void k_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
 // source address / validity address, per column the main and changelog
 // output pointers and the output width, are staged in LDS once per block
 // (pmh_fold_cl_lds bytes; plan creation refuses a section whose tables exceed
-// PMH_FOLD_CL_LDS_MAX or whose columns are paged). Data moves through
+// PMH_FOLD_CL_LDS_MAX). Data moves through
 // address_space(1) pointers.
 constexpr int FOLD_CL_THREADS = 256;
 constexpr int FOLD_CL_G = 4;  // columns whose loads are in flight together
@@ -4610,12 +4419,7 @@ DEV FoldClTables fold_cl_stage(uint64_t *smem, const DevCol *cols,
         t.valid[e] = cols[e].valid0;
     }
     for (int c = threadIdx.x; c < n_cols; c += FOLD_CL_THREADS) {
-        const int dt = col_dtype[c];
-        t.width[c] = dt == 1 ? 1
-                     : dt == 2 ? 2
-                     : (dt == 3 || dt == 5 || dt == 7) ? 4
-                     : (dt == 4 || dt == 6) ? 8
-                                            : 0;
+        t.width[c] = (uint8_t)pmh_out_width(col_dtype[c]);
         t.out[c] = (uint64_t)out_ptrs[c];
         t.ov[c] = col_nullable[c] ? (uint64_t)out_valid[c] : 0;
         t.out2[c] = out_ptrs2 ? (uint64_t)out_ptrs2[c] : 0;
@@ -5560,16 +5364,17 @@ static int g_last_emit_kernel = PMH_EMIT_NONE;
 int pmh_last_emit_kernel() { return g_last_emit_kernel; }
 
 // Winner emit. Three kernels, most specific first:
-//  - k_emit_stream (tile slices streamed through LDS, no gather) when the
-//    plan is all-contiguous, every run slot a winner can name is a merge run
-//    (n_desc == k: a lookup winner may name a slot outside the tile's
-//    slices), n_cols <= 256, no emitted column is nullable (validity is not
-//    streamed), the tables fit, and PMH_EMIT_STREAM is not 0;
-//  - k_emit_contig for the other all-contiguous plans whose tables fit;
-//  - k_emit for the rest, and under PMH_EMIT_LEGACY=1.
+//  - k_emit_stream (tile slices streamed through LDS, no gather) when every
+//    run slot a winner can name is a merge run (n_desc == k: a lookup winner
+//    may name a slot outside the tile's slices), n_cols <= 256, no emitted
+//    column is nullable (validity is not streamed), the tables fit, and
+//    PMH_EMIT_STREAM is not 0;
+//  - k_emit_contig (descriptors in LDS) for the other plans whose tables fit;
+//  - k_emit (descriptors read from global memory) for the rest, such as 32
+//    runs x 32 columns, and under PMH_EMIT_LEGACY=1.
 hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
                            const uint8_t *col_nullable, int any_nullable,
-                           int n_cols, int k, int n_desc, int contiguous,
+                           int n_cols, int k, int n_desc,
                            const int32_t *cuts, const int64_t *lens,
                            const uint32_t *winners,
                            const int32_t *tile_counts,
@@ -5596,10 +5401,9 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
     if (n_emit < 0 || n_emit > n_cols) n_emit = n_cols;
     const int grid = emit_grid();
     const int64_t lds = emit_contig_lds(n_desc, n_cols);
-    // k_emit_contig serves all-contiguous plans whose tables fit; position ->
-    // column bytes cap n_cols at 256
-    const bool contig = contiguous && n_desc >= 1 && n_cols <= 256 &&
-                        lds <= EMIT_LDS_MAX &&
+    // k_emit_contig serves plans whose tables fit; position -> column bytes
+    // cap n_cols at 256
+    const bool contig = n_desc >= 1 && n_cols <= 256 && lds <= EMIT_LDS_MAX &&
                         env_int("PMH_EMIT_LEGACY", 0) == 0;
     const int64_t tables = emit_stream_tables(k, n_cols);
     const bool streamed = contig && n_desc == k && !any_nullable &&
@@ -5643,7 +5447,7 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
         g_last_emit_kernel = PMH_EMIT_STREAM;
         return hipGetLastError();
     }
-    g_last_emit_kernel = contig ? PMH_EMIT_CONTIG : PMH_EMIT_PAGED;
+    g_last_emit_kernel = contig ? PMH_EMIT_CONTIG : PMH_EMIT_GATHER;
     if (contig) {
         auto launch = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(EMIT_THREADS), (size_t)lds,

@@ -24,6 +24,7 @@
 #include "../../include/paimon_hip.h"
 #include "changelog_core.h"
 #include "codec.h"
+#include "column_core.h"
 #include "zstd_core.h"
 #include <map>
 #include "common.h"
@@ -543,9 +544,6 @@ struct GatherTask {
 
 struct RunCol {
     void *contig = nullptr;
-    std::vector<DevPage> pages_host;
-    DevPage *pages_dev = nullptr;
-    int n_pages = 0;
     bool dict_encoded = false;  // any dictionary-encoded chunk
     std::vector<RleChunk> rle_host;
     RleChunk *rle_dev = nullptr;
@@ -611,9 +609,6 @@ struct Section {
     DevCol *seq_cols = nullptr;   // [k]
     DevCol *kind_cols = nullptr;  // [k]
     DevCol *all_cols = nullptr;   // [k * n_cols] run-major
-    // every descriptor built for this section (real runs + lookup slots) has
-    // n_pages == 1: the emit gather may address columns directly
-    bool cols_contig = true;
     int64_t *lens_dev = nullptr;
     int32_t *cuts = nullptr;
     uint32_t *winners = nullptr;
@@ -873,33 +868,6 @@ static const char *logical_name(int lt) {
     case PMH_LT_TIMESTAMP_LTZ_MICROS: return "timestamp_ltz(6)";
     }
     return "none";
-}
-
-static int dtype_out_esize(int dt) {
-    switch (dt) {
-    case PMH_DT_INT8: return 1;
-    case PMH_DT_INT16: return 2;
-    case PMH_DT_INT32: return 4;
-    case PMH_DT_INT64: return 8;
-    case PMH_DT_FLOAT32: return 4;
-    case PMH_DT_FLOAT64: return 8;
-    case PMH_DT_STRING: return 4;  // global dictionary ids
-    }
-    return 0;
-}
-
-static int dtype_stored_esize(int dt) {
-    // parquet physical widths: INT8/16/32 stored as INT32
-    switch (dt) {
-    case PMH_DT_INT8:
-    case PMH_DT_INT16:
-    case PMH_DT_INT32: return 4;
-    case PMH_DT_INT64: return 8;
-    case PMH_DT_FLOAT32: return 4;
-    case PMH_DT_FLOAT64: return 8;
-    case PMH_DT_STRING: return 4;  // the RLE id streams decode to int32
-    }
-    return 0;
 }
 
 static int expected_phys(int dtype) {
@@ -2540,14 +2508,6 @@ static bool stage_run(pmh_plan_t *plan, const std::vector<FileDesc> &files,
                 vu.scale_addr =
                     (uint64_t)(rc.scale_dev + (vu.scale_addr - 1));
         }
-        DevPage dp{(uint64_t)rc.contig, 0};
-        rc.pages_host.assign(1, dp);
-        rc.n_pages = 1;
-        rc.pages_dev = (DevPage *)plan->bufs.alloc(sizeof(DevPage));
-        if (!rc.pages_dev) return false;
-        if (hipMemcpy(rc.pages_dev, rc.pages_host.data(), sizeof(DevPage),
-                      hipMemcpyHostToDevice) != hipSuccess)
-            return false;
     }
     return true;
 }
@@ -2698,8 +2658,7 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
                 valids[c] = (uint8_t *)plan->bufs.alloc(sec.brows[b]);
                 if (!valids[c]) return false;
             }
-            DevCol dc{(uint64_t)outs[c], (uint64_t)valids[c], nullptr, 1,
-                      es};
+            DevCol dc{(uint64_t)outs[c], (uint64_t)valids[c], es, 0};
             vall[b * n_cols + c] = dc;
             if (c == 0) vkeys[b] = dc;
             if (c == seq_idx) vseqs[b] = dc;
@@ -2763,10 +2722,8 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
         for (int c = 0; c < n_cols; c++) {
             DevCol dc{(uint64_t)run.cols[c].contig,
                       (uint64_t)run.cols[c].valid_dev,
-                      run.cols[c].pages_dev, run.cols[c].n_pages,
-                      plan->cols[c].stored_esize};
+                      plan->cols[c].stored_esize, 0};
             allv[r * n_cols + c] = dc;
-            sec.cols_contig &= dc.n_pages == 1;
             if (c == 0) keyv[r] = dc;  // single-column key: the column itself
             if (c == seq_idx) seqv[r] = dc;
             if (c == kind_idx) kindv[r] = dc;
@@ -2777,7 +2734,7 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
             int64_t n = run.length > 0 ? run.length : 1;
             sec.ckeys[r] = (int64_t *)plan->bufs.alloc(n * 8);
             if (!sec.ckeys[r]) return false;
-            keyv[r] = DevCol{(uint64_t)sec.ckeys[r], 0, nullptr, 1, 8};
+            keyv[r] = DevCol{(uint64_t)sec.ckeys[r], 0, 8, 0};
         }
     }
     sec.n_tiles = (sec.total_rows + PMH_TILE_ROWS - 1) / PMH_TILE_ROWS;
@@ -3150,8 +3107,8 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 set_error("bad column spec");
                 return false;
             }
-            cs.out_esize = dtype_out_esize(cs.dtype);
-            cs.stored_esize = dtype_stored_esize(cs.dtype);
+            cs.out_esize = pmh_out_width(cs.dtype);
+            cs.stored_esize = pmh_stored_width(cs.dtype);
             plan->cols.push_back(cs);
             return true;
         };
@@ -3706,14 +3663,13 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 return nullptr;
             if (plan->cl_fold) {
                 // the folded changelog kernels keep per-run column tables in
-                // LDS and address columns directly
+                // LDS
                 const int64_t lds = pmh_fold_cl_lds(
                     (int64_t)sec.runs.size(), (int64_t)plan->cols.size());
-                if (!sec.cols_contig || lds > PMH_FOLD_CL_LDS_MAX) {
+                if (lds > PMH_FOLD_CL_LDS_MAX) {
                     set_error("changelog_producer=full-compaction with the "
                               "%s engine: a section of %zu runs x %zu columns "
-                              "needs %lld bytes of column tables (limit %lld) "
-                              "and contiguous columns",
+                              "needs %lld bytes of column tables (limit %lld)",
                               plan->agg ? "aggregation" : "partial-update",
                               sec.runs.size(), plan->cols.size(),
                               (long long)lds,
@@ -4038,8 +3994,8 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
             if (hb != hipSuccess) return fail("hier scan", hb);
             hb = pmh_launch_emit(sec.rall + (size_t)lo * n_cols,
                                  p->hier_dtype_dev, p->col_nullable_dev,
-                                 any_nullable, n_cols, kb, kb,
-                                 sec.cols_contig, sec.cuts, sec.rlens + lo,
+                                 any_nullable, n_cols, kb, kb, sec.cuts,
+                                 sec.rlens + lo,
                                  sec.winners, sec.tile_counts,
                                  sec.tile_offsets, btiles, PMH_TILE_ROWS,
                                  sec.lens_dev + b, sec.bout_ptrs[b],
@@ -4211,8 +4167,7 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
         // runs; a hierarchical chain reads its (contiguous) virtual runs
         e = pmh_launch_emit(sec.all_cols, p->col_dtype_dev,
                             p->col_nullable_dev, any_nullable, n_cols, k,
-                            sec.hier ? k : k + sec.n_lookup,
-                            sec.hier || sec.cols_contig, sec.cuts,
+                            sec.hier ? k : k + sec.n_lookup, sec.cuts,
                             sec.lens_dev, sec.winners,
                             sec.tile_counts, sec.tile_offsets, n_tiles_eff,
                             PMH_TILE_ROWS, sec.total_dev, p->out_ptrs_dev,
@@ -5358,9 +5313,7 @@ int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
         std::vector<DevCol> cols(k);
         bool ok = true;
         for (int r = 0; r < k && ok; r++) {
-            DevCol c{};
-            c.n_pages = 1;
-            c.esize = key_width;
+            DevCol c{0, 0, key_width, 0};
             if (lens[r] > 0) {  // an empty run keeps a null address
                 const size_t nb = (size_t)lens[r] * key_width;
                 void *d = dalloc(nb);

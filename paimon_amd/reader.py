@@ -543,11 +543,11 @@ def debug_partition(runs, tile_rows, mode=PARTITION_HOST):
     return cuts
 
 
-EMIT_NONE, EMIT_PAGED, EMIT_CONTIG, EMIT_STREAM = 0, 1, 2, 3
+EMIT_NONE, EMIT_GATHER, EMIT_CONTIG, EMIT_STREAM = 0, 1, 2, 3
 
 
 def debug_last_emit_kernel():
-    """The kernel the last winner emit of this process ran: EMIT_PAGED
+    """The kernel the last winner emit of this process ran: EMIT_GATHER
     (k_emit), EMIT_CONTIG (k_emit_contig), EMIT_STREAM (k_emit_stream), or
     EMIT_NONE before the first one."""
     lib = load_lib()

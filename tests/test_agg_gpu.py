@@ -9,6 +9,8 @@ from oracle import aggregation_model
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import gen_runs_partial_update, write_runs
 
+import tests.column_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 KEY_COLS = [{"name": "_KEY_k", "type": "int64"}]
@@ -307,3 +309,34 @@ class TestAggregationRetracts:
                                aggregations={"v_c0": "sum"}) as plan:
                 with pytest.raises(RuntimeError, match="aggregation"):
                     _read_all(plan)
+
+
+class TestColumnDtypes:
+    """Every column dtype, without nulls and (one column per output width)
+    with them, through k_emit_agg, at the default emit grid and at seven
+    blocks. Shape and columns: tests/column_cases.py. No integer sum: the
+    values span their types' whole range."""
+
+    AGGS = {"v_i8": "max", "v_i16": "min", "v_i32": "last_value",
+            "v_i64": "first_value", "v_f32": "sum", "v_f64": "max",
+            "n_i8": "first_non_null_value", "n_i32": "max", "n_i64": "min"}
+
+    @pytest.mark.parametrize("nulls", [True, False])
+    def test_aggregation(self, tmp_path, monkeypatch, nulls):
+        # nulls=False: k_emit_agg<false>, the instantiation without row masks
+        runs = cc.gen(621, nulls=nulls)
+        metas = cc.write(runs, str(tmp_path))
+        exp = aggregation_model(
+            runs, [self.AGGS.get(nm, "last_non_null_value")
+                   for nm in cc.NAMES])
+        for blocks in cc.EMIT_BLOCKS:
+            monkeypatch.delenv("PMH_EMIT_BLOCKS", raising=False)
+            if blocks:
+                monkeypatch.setenv("PMH_EMIT_BLOCKS", blocks)
+            with Session(0) as s:
+                with MergeReadPlan(s, file_descs_from_metas(metas),
+                                   cc.KEY_COLS, cc.VALUE_COLS,
+                                   merge_engine="aggregation",
+                                   aggregations=self.AGGS) as plan:
+                    got = cc.read_all(plan)
+            cc.check(got, exp, f"blocks {blocks}")

@@ -32,6 +32,8 @@ from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import write_runs
 from tests.changelog_fold_model import fold_changelog, rows_to_columns
 
+import tests.column_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 KEY_COLS = [{"name": "_KEY_k", "type": "int64"}]
@@ -319,3 +321,30 @@ class TestAggregation:
                        aggregations={"v_c0": "sum", "v_c1": "max",
                                      "v_c2": "last_non_null_value"}),
                   require=(I, UB, UA, D))
+
+
+class TestColumnDtypes:
+    """Every column dtype, without nulls and (one column per output width)
+    with them, through k_cl_finalize_out / k_cl_emit_out behind k_emit_pu:
+    before-type rows from the source columns, after-type rows from the main
+    output, at the default emit grid and at seven blocks. Shape and columns:
+    tests/column_cases.py."""
+
+    def test_partial_update_changelog(self, tmp_path, monkeypatch):
+        runs = cc.gen(641, top=True)
+        levels = [0] * (cc.N_RUNS - 1) + [MAX_LEVEL]
+        metas = cc.write(runs, str(tmp_path), levels)
+        cl_rows, exp_cl, exp_main = _expected(runs, levels, _pu, False, True)
+        assert {r[2] for r in cl_rows} == {I, UB, UA}
+        for blocks in cc.EMIT_BLOCKS:
+            monkeypatch.delenv("PMH_EMIT_BLOCKS", raising=False)
+            if blocks:
+                monkeypatch.setenv("PMH_EMIT_BLOCKS", blocks)
+            with Session(0) as s:
+                with MergeReadPlan(s, file_descs_from_metas(metas),
+                                   cc.KEY_COLS, cc.VALUE_COLS,
+                                   changelog_producer="full-compaction",
+                                   max_level=MAX_LEVEL, **PU_KW) as plan:
+                    main, cl = cc.read_all(plan, changelog=True)
+            cc.check(cl, exp_cl, f"changelog, blocks {blocks}", dicts=main)
+            cc.check(main, exp_main, f"main, blocks {blocks}")

@@ -9,6 +9,8 @@ from oracle import full_changelog_model
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import gen_runs_dedup, write_runs
 
+import tests.column_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 KEY_COLS = [{"name": "_KEY_k", "type": "int64"}]
@@ -257,3 +259,26 @@ class TestRowDedupWithNulls:
             (len(cl["_KEY_k"]), len(exp_keys))
         assert (cl["_KEY_k"] == exp_keys).all()
         assert (cl["_VALUE_KIND"] == ck).all()
+
+
+class TestColumnDtypes:
+    """Every column dtype, without nulls and (one column per output width)
+    with them, through k_cl_emit: the changelog rows and the main batch of a
+    deduplicate plan against the oracle's records. Shape and columns:
+    tests/column_cases.py."""
+
+    def test_changelog_rows(self, tmp_path):
+        runs = cc.gen(631, kinds=(0, 3), kind_p=[0.85, 0.15], top=True)
+        levels = [0] * (cc.N_RUNS - 1) + [MAX_LEVEL]
+        metas = cc.write(runs, str(tmp_path), levels)
+        (cr, cw, ck), (rr, rw) = full_changelog_model(runs, levels, MAX_LEVEL)
+        assert set(np.unique(ck)) == {0, 1, 2, 3}
+        with Session(0) as s:
+            with MergeReadPlan(s, file_descs_from_metas(metas), cc.KEY_COLS,
+                               cc.VALUE_COLS,
+                               changelog_producer="full-compaction",
+                               max_level=MAX_LEVEL) as plan:
+                main, cl = cc.read_all(plan, changelog=True)
+        cc.check(cl, cc.gather(runs, cr, cw, kind=ck), "changelog",
+                 dicts=main)
+        cc.check(main, cc.gather(runs, rr, rw), "main")

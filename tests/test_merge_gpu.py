@@ -12,6 +12,9 @@ import pytest
 from oracle import merge_dedup
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import gen_runs_dedup, write_runs
+from paimon_amd.reader import EMIT_GATHER, debug_last_emit_kernel
+
+import tests.column_cases as cc
 
 pytestmark = pytest.mark.gpu
 
@@ -861,3 +864,48 @@ class TestHierarchicalCrosses:
         runs = gen_runs_dedup(34, 4_000, n_value_cols=2, seed=992,
                               delete_frac=0.15)
         _run_and_compare(tmp_path, runs, compression="zstd")
+
+
+class TestColumnDtypes:
+    """Every column dtype, without nulls and (one column per output width)
+    with them, through each winner emit that reads columns by descriptor:
+    k_emit (the chain under PMH_EMIT_LEGACY=1), k_merge_emit + k_emit_dense
+    (fused split pair), k_merge_emit emitting in-kernel by direct gather and
+    through its LDS slabs (PMH_FSTAGE=1). Shape and columns:
+    tests/column_cases.py; compared with the oracle's winners."""
+
+    PATHS = {
+        "k_emit": {"PMH_EMIT_LEGACY": "1"},
+        "fused_split": {"PMH_FUSED": "1"},
+        "fused_inkernel": {"PMH_FUSED": "1", "PMH_FSPLIT": "0"},
+        "fused_staged": {"PMH_FUSED": "1", "PMH_FSPLIT": "0",
+                         "PMH_FSTAGE": "1"},
+    }
+
+    @pytest.fixture(scope="class")
+    def case(self, tmp_path_factory):
+        runs = cc.gen(601, kinds=(0, 3), kind_p=[0.85, 0.15])
+        metas = cc.write(runs, str(tmp_path_factory.mktemp("dtypes")))
+        r, w = merge_dedup(runs, drop_delete=True)
+        return metas, cc.gather(runs, r, w)
+
+    @pytest.mark.parametrize("blocks", cc.EMIT_BLOCKS)
+    @pytest.mark.parametrize("path", list(PATHS))
+    def test_every_dtype(self, case, monkeypatch, path, blocks):
+        metas, exp = case
+        for k in ("PMH_EMIT_LEGACY", "PMH_FUSED", "PMH_FSPLIT", "PMH_FSTAGE",
+                  "PMH_EMIT_BLOCKS"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in self.PATHS[path].items():
+            monkeypatch.setenv(k, v)
+        if blocks:
+            monkeypatch.setenv("PMH_EMIT_BLOCKS", blocks)
+        with Session(0) as s:
+            with MergeReadPlan(s, file_descs_from_metas(metas), cc.KEY_COLS,
+                               cc.VALUE_COLS) as plan:
+                got = cc.read_all(plan)
+                mode = plan.stats().get("path_mode", 0)
+        assert mode == {"k_emit": 0, "fused_split": 2}.get(path, 1)
+        if path == "k_emit":
+            assert debug_last_emit_kernel() == EMIT_GATHER
+        cc.check(got, exp, f"{path} blocks {blocks}")

@@ -9,6 +9,8 @@ from oracle import merge_dedup, partial_update_model
 from paimon_amd import Session, MergeReadPlan, file_descs_from_metas
 from paimon_amd.datagen import gen_runs_dedup, gen_runs_partial_update, write_runs
 
+import tests.column_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 KEY_COLS = [{"name": "_KEY_k", "type": "int64"}]
@@ -397,3 +399,47 @@ class TestSequenceGroups:
                                    "group_fields": ["v_c1"]},
                                   {"sequence_fields": ["v_c1"],
                                    "group_fields": ["v_c2"]}])
+
+
+class TestColumnDtypes:
+    """Every column dtype, without nulls and (one column per output width)
+    with them, through k_emit_pu and k_emit_pu_sg, at the default emit grid
+    and at seven blocks. Shape and columns: tests/column_cases.py."""
+
+    # (n_i32, n_i64) orders {n_i8, n_i16}. The group's fields are columns with
+    # nulls: a retract nulls them, and a plan has a validity output only for
+    # columns with staged nulls. Every other column is a plain one.
+    SG_NAMED = [{"sequence_fields": ["n_i32", "n_i64"],
+                 "group_fields": ["n_i8", "n_i16"]}]
+
+    def _read(self, monkeypatch, metas, blocks, **kw):
+        monkeypatch.delenv("PMH_EMIT_BLOCKS", raising=False)
+        if blocks:
+            monkeypatch.setenv("PMH_EMIT_BLOCKS", blocks)
+        with Session(0) as s:
+            with MergeReadPlan(s, file_descs_from_metas(metas), cc.KEY_COLS,
+                               cc.VALUE_COLS, merge_engine="partial-update",
+                               **kw) as plan:
+                return cc.read_all(plan)
+
+    @pytest.mark.parametrize("nulls", [True, False])
+    def test_partial_update(self, tmp_path, monkeypatch, nulls):
+        # nulls=False: k_emit_pu<false>, the instantiation without row masks
+        runs = cc.gen(611, nulls=nulls)
+        metas = cc.write(runs, str(tmp_path))
+        exp = partial_update_model(runs)
+        for blocks in cc.EMIT_BLOCKS:
+            cc.check(self._read(monkeypatch, metas, blocks), exp,
+                     f"blocks {blocks}")
+
+    def test_sequence_groups(self, tmp_path, monkeypatch):
+        from oracle import partial_update_seqgroup_model
+        runs = cc.gen(612, kinds=(0, 2, 1, 3), kind_p=[0.6, 0.1, 0.15, 0.15])
+        metas = cc.write(runs, str(tmp_path))
+        sg_idx = [{k: [cc.index_of(nm) for nm in v] for k, v in g.items()}
+                  for g in self.SG_NAMED]
+        exp = partial_update_seqgroup_model(runs, sg_idx, drop_delete=True)
+        for blocks in cc.EMIT_BLOCKS:
+            cc.check(self._read(monkeypatch, metas, blocks,
+                                sequence_groups=self.SG_NAMED), exp,
+                     f"blocks {blocks}")
