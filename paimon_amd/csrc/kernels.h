@@ -53,7 +53,168 @@ struct DevCol {
 // RleChunk, Rlev2Chunk, DeltaChunk, DeltaStream: stream_core.h (the host
 // walks that fill them live there).
 
-extern "C" {
+// ------------------------------------------------------------ merge flag word
+// The `flags` argument of the merge and folding-emit launchers. The plan
+// builds its engine bits once at creation; the profiling fields are added per
+// read from the environment. Every launcher of a read gets the same word: the
+// folding emit kernels read only RROD, IGNORE_DELETE and AGG_RETRACT from it.
+constexpr int PMH_FLAG_DROP_DELETE = 1 << 0;    // drop groups that end deleted
+constexpr int PMH_FLAG_IGNORE_DELETE = 1 << 1;  // skip retract records
+constexpr int PMH_FLAG_MEMBERS = 1 << 2;   // member lists (partial-update /
+                                           // aggregation) instead of winners
+constexpr int PMH_FLAG_FIRST_ROW = 1 << 3;      // first-row engine
+constexpr int PMH_FLAG_RROD = 1 << 4;           // remove-record-on-delete
+constexpr int PMH_FLAG_SEQ_GROUPS = 1 << 5;     // sequence groups
+constexpr int PMH_FLAG_AGG_RETRACT = 1 << 6;    // every aggregator retracts
+constexpr int PMH_FLAG_CL_ROW_DEDUP = 1 << 7;   // changelog row-deduplicate
+// profiling-only fields, (flags >> SHIFT) & MASK:
+constexpr int PMH_FLAG_ABLATE_SHIFT = 8;   // PMH_ABLATE: k_merge_tiles phases
+constexpr int PMH_FLAG_ABLATE_MASK = 0xf;
+constexpr int PMH_FLAG_FABL_SHIFT = 12;    // PMH_FABL: k_merge_emit phases
+constexpr int PMH_FLAG_FABL_MASK = 0x3;
+constexpr int PMH_FLAG_FSTAGE_SHIFT = 14;  // PMH_FSTAGE: LDS-staged emission
+constexpr int PMH_FLAG_FSTAGE_MASK = 1;
+// lookup changelog producer (LookupChangelogMergeFunctionWrapper): the lookup
+// walk of k_merge_tiles. The run tables then hold RunSet::n_slots > k slots
+// (the lookup levels after the k merge runs) and the probe words come from
+// pmh_launch_lookup_probe.
+constexpr int PMH_FLAG_LOOKUP = 1 << 15;
+// full-compaction changelog of a folding engine: the changelog walk of the
+// member-list k_merge_tiles (see pmh_launch_cl_finalize_out)
+constexpr int PMH_FLAG_FOLD_CL = 1 << 16;
+
+// ----------------------------------------------------------- device error word
+// One uint32 per section (TileSet::err), OR-ed by the kernels and read back
+// after every pass. Bits 0-3 are the merge kernels'; the ORC decode bits sit
+// above them (ODC_ERR_*, orc_decimal_core.h; OTS_ERR_*, orc_timestamp_core.h).
+constexpr uint32_t PMH_ERR_RETRACT = 1u << 0;       // engine rejects retracts
+constexpr uint32_t PMH_ERR_FIRST_ROW_RETRACT = 1u << 1;
+constexpr uint32_t PMH_ERR_LOOKBACK = 1u << 2;      // fused lookback timed out
+constexpr uint32_t PMH_ERR_TOP_LEVEL_DUP = 1u << 3; // two max_level records
+
+// ------------------------------------------------------- launcher arguments
+// Plain views of device memory the plan owns. A Section and the plan hold
+// them filled; a launcher takes the ones its kernel reads and unpacks them
+// into the kernel's argument list.
+
+// A section's sorted runs: [n_slots] tables, the k merge runs first.
+struct RunSet {
+    const DevCol *keys = nullptr;   // merge comparand (a packed composite
+                                    // key column for multi-column keys)
+    const DevCol *seqs = nullptr;
+    const DevCol *kinds = nullptr;
+    const DevCol *cols = nullptr;   // [n_slots * n_cols] run-major
+    int64_t *lens = nullptr;
+    const uint64_t *tombs = nullptr;   // per-run tombstone bytes, or null
+    const uint8_t *levels = nullptr;   // per-run level (changelog plans)
+    uint64_t *const *masks = nullptr;  // [k] packed row validity (k_pack_valid;
+                                       // folding engines), or null: walk the
+                                       // per-column bytes (> 64 columns)
+    int k = 0;        // merge runs
+    int n_slots = 0;  // k + lookup-level slots a winner word can name
+    int n_cols = 0;
+    // runs [lo, lo + n) as a set of their own (hierarchical batches)
+    RunSet sub(int lo, int n) const {
+        RunSet r = *this;
+        r.keys += lo;
+        r.seqs += lo;
+        r.kinds += lo;
+        r.cols += (size_t)lo * n_cols;
+        r.lens += lo;
+        if (tombs) r.tombs += lo;
+        if (levels) r.levels += lo;
+        if (masks) r.masks += lo;
+        r.k = r.n_slots = n;
+        return r;
+    }
+};
+
+// The plan's columns: key..., seq, kind, value...
+struct ColumnSet {
+    const uint8_t *dtype = nullptr;     // [n_cols] pmh_dtype codes
+    const uint8_t *nullable = nullptr;  // [n_cols] 1 = has a validity output
+    const uint8_t *agg = nullptr;       // [n_cols] PMH_AGG_* (aggregation)
+    const int16_t *useq = nullptr;      // [n_useq] sequence.field columns
+    int n_useq = 0;
+    int any_nullable = 0;  // some column is nullable
+    int n_cols = 0;
+    int n_key_cols = 1;
+    int seq_col() const { return n_key_cols; }
+    int kind_col() const { return n_key_cols + 1; }
+    int first_val() const { return n_key_cols + 2; }
+    // the single key column, -1 for composite keys (their key columns emit
+    // through the generic column path)
+    int key_col() const { return n_key_cols > 1 ? -1 : 0; }
+};
+
+// partial-update sequence groups: col_group[c] = group id or 0xff; fields
+// packs 4 sequence-field column indices per group
+struct SeqGroupSet {
+    const uint8_t *col_group = nullptr;
+    const int16_t *fields = nullptr;
+    const uint8_t *nseq = nullptr;
+    int n_groups = 0;
+};
+
+// A section's tile state. Every tile holds PMH_TILE_ROWS merged rows.
+struct TileSet {
+    int32_t *cuts = nullptr;        // [(n_tiles + 1) * k] partition cuts
+    int64_t n_tiles = 0;
+    uint32_t *winners = nullptr;    // packed (run, row) winners / members
+    int32_t *counts = nullptr;      // [n_tiles] rows out per tile
+    int64_t *offsets = nullptr;     // [n_tiles] exclusive scan of counts
+    int64_t *total = nullptr;       // rows out
+    uint16_t *group_start = nullptr;  // member-list group offsets
+    uint32_t *err = nullptr;        // the section's error word (PMH_ERR_*)
+    // fused path: per-tile lookback words and the tile ticket (zeroed before
+    // every launch), dense winner list of the split mode
+    uint64_t *status = nullptr;
+    uint64_t *ticket = nullptr;
+    uint32_t *dense_winners = nullptr;
+    // the first n tiles, counting their rows into total_out
+    TileSet first(int64_t n, int64_t *total_out) const {
+        TileSet t = *this;
+        t.n_tiles = n;
+        t.total = total_out;
+        return t;
+    }
+};
+
+// One output batch: [n_cols] device arrays of column pointers
+struct OutputSet {
+    void *const *ptrs = nullptr;
+    uint8_t *const *valid = nullptr;  // null entries: column never null
+};
+
+// Changelog chain state of a section (both producers)
+struct ChangelogSet {
+    uint64_t *entries = nullptr;  // 2 slots per group, provisional
+    uint64_t *rows = nullptr;     // compacted rows (k_cl_finalize*)
+    int32_t *counts = nullptr;
+    int64_t *offsets = nullptr;
+    int64_t *total = nullptr;
+    int max_level = 0;
+};
+
+// Lookup probe words of a section: off[r] >= 0 is the word offset of run r's
+// first row, < 0 means run r is not probed (not level 0)
+struct ProbeSet {
+    const int64_t *off = nullptr;
+    uint32_t *words = nullptr;
+    int n_levels = 0;
+    int64_t max_rows = 0;  // longest probed run
+};
+
+// Grid of a grid-stride launch over `want` work items: one block each, at
+// least 1 and at most `cap` (4096 unless the kernel says otherwise).
+inline int pmh_grid(int64_t want, int cap = 4096) {
+    return want < cap ? (int)(want > 0 ? want : 1) : cap;
+}
+
+// ------------------------------------------------------------------ launchers
+// Internal to the library (the exported C ABI is include/paimon_hip.h). A
+// merge / emit / changelog launcher takes the argument structs its kernel
+// reads, the flag word where the kernel has one, and the stream.
 
 // DELTA_BINARY_PACKED decode, three phases batched across all chunks:
 // per-block delta sums, per-stream base scan, then unpack + wave scan +
@@ -89,50 +250,38 @@ hipError_t pmh_launch_filter(const DevCol *cols, int n_cols,
 
 // full-compaction changelog chain (FullChangelogMergeFunctionWrapper):
 // finalize compacts the merge pass's provisional per-group entries into
-// rows (evaluating row-deduplicate value equality); emit gathers them.
-hipError_t pmh_launch_cl_finalize(const DevCol *cols,
-                                  const uint8_t *col_dtype, int n_cols,
-                                  int first_val, int k,
-                                  const uint64_t *cl_entries,
-                                  uint64_t *cl_out, int32_t *cl_counts,
-                                  int64_t n_tiles, int64_t tile_rows,
+// rows (evaluating row-deduplicate value equality); emit gathers them into
+// the changelog batch `out2`.
+hipError_t pmh_launch_cl_finalize(const RunSet &runs, const ColumnSet &columns,
+                                  const TileSet &tiles, const ChangelogSet &cl,
                                   hipStream_t stream);
-hipError_t pmh_launch_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
-                              const uint8_t *col_nullable, int n_cols,
-                              int kind_col, const uint64_t *cl_rows,
-                              const int32_t *cl_counts,
-                              const int64_t *cl_offsets, int64_t n_tiles,
-                              int64_t tile_rows, void *const *out_ptrs,
-                              uint8_t *const *out_valid, hipStream_t stream);
+hipError_t pmh_launch_cl_emit(const RunSet &runs, const ColumnSet &columns,
+                              const TileSet &tiles, const ChangelogSet &cl,
+                              const OutputSet &out2, hipStream_t stream);
 
 // The same chain for the folding engines (partial-update / aggregation),
-// whose after-type rows are the engine's folded result: merge flags bit
-// PMH_FLAG_FOLD_CL selects the changelog walk of the PU k_merge_tiles, whose
-// after-type entries name the main-output row tile_offsets[tile] + g
+// whose after-type rows are the engine's folded result: PMH_FLAG_FOLD_CL
+// selects the changelog walk of the member-list k_merge_tiles, whose
+// after-type entries name the main-output row tiles.offsets[tile] + g
 // (changelog_core.h). Both kernels therefore run after the engine's emit
-// kernel on the same stream and read out_ptrs / out_valid (the plan's main
-// output); emit writes out_ptrs2 / out_valid2. They stage pmh_fold_cl_lds(k,
-// n_cols) bytes of per-run column tables in LDS; the launchers return
-// hipErrorInvalidValue past PMH_FOLD_CL_LDS_MAX (plan creation refuses such a
-// section first).
-constexpr int PMH_FLAG_FOLD_CL = 1 << 16;
+// kernel on the same stream and read `out` (the plan's main output); emit
+// writes `out2`. They stage pmh_fold_cl_lds(k, n_cols) bytes of per-run column
+// tables in LDS; the launchers return hipErrorInvalidValue past
+// PMH_FOLD_CL_LDS_MAX (plan creation refuses such a section first).
 constexpr int64_t PMH_FOLD_CL_LDS_MAX = 48 * 1024;
 constexpr int64_t pmh_fold_cl_lds(int64_t k, int64_t n_cols) {
     return 16 * k * n_cols + 32 * n_cols + ((n_cols + 7) & ~(int64_t)7);
 }
-hipError_t pmh_launch_cl_finalize_out(
-    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
-    int n_cols, int first_val, int k, const uint64_t *cl_entries,
-    uint64_t *cl_out, int32_t *cl_counts, const int64_t *tile_offsets,
-    int64_t n_tiles, int64_t tile_rows, void *const *out_ptrs,
-    uint8_t *const *out_valid, hipStream_t stream);
-hipError_t pmh_launch_cl_emit_out(
-    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
-    int n_cols, int k, int kind_col, const uint64_t *cl_rows,
-    const int32_t *cl_counts, const int64_t *cl_offsets,
-    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
-    void *const *out_ptrs, uint8_t *const *out_valid, void *const *out_ptrs2,
-    uint8_t *const *out_valid2, hipStream_t stream);
+hipError_t pmh_launch_cl_finalize_out(const RunSet &runs,
+                                      const ColumnSet &columns,
+                                      const TileSet &tiles,
+                                      const ChangelogSet &cl,
+                                      const OutputSet &out,
+                                      hipStream_t stream);
+hipError_t pmh_launch_cl_emit_out(const RunSet &runs, const ColumnSet &columns,
+                                  const TileSet &tiles, const ChangelogSet &cl,
+                                  const OutputSet &out, const OutputSet &out2,
+                                  hipStream_t stream);
 
 // on-GPU zstd page decompression (k_zstd_pages): one job per parquet page.
 // scratch must hold n_jobs * PZ_SLOT bytes (PZ_SLOT in zstd_core.h);
@@ -181,33 +330,18 @@ hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
                                 int64_t total_rows, int32_t *cuts,
                                 hipStream_t stream);
 
-hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
-                                  const DevCol *kinds, const int64_t *lens,
-                                  int k, const int32_t *cuts, int64_t n_tiles,
-                                  int64_t tile_rows, int flags,
-                                  const uint64_t *tombs,
-                                  uint32_t *winners, int32_t *tile_counts,
-                                  uint16_t *group_start, uint32_t *err_flag,
-                                  const uint8_t *run_levels, int max_level,
-                                  uint64_t *cl_entries, int32_t *cl_counts,
-                                  const uint32_t *probe_words,
-                                  const int64_t *probe_off,
-                                  hipStream_t stream);
+// Tile merge: winners (or member lists, PMH_FLAG_MEMBERS) and per-tile
+// counts into `tiles`. cl / probe are the section's changelog and lookup
+// state; a plan without them passes them empty.
+hipError_t pmh_launch_merge_tiles(const RunSet &runs, const TileSet &tiles,
+                                  int flags, const ChangelogSet &cl,
+                                  const ProbeSet &probe, hipStream_t stream);
 
-// lookup changelog producer (LookupChangelogMergeFunctionWrapper): merge
-// flags bit selecting the lookup walk of k_merge_tiles. keys/seqs/kinds/
-// run_levels then hold k + n_levels slots (the lookup levels after the k
-// merge runs) and probe_words/probe_off come from pmh_launch_lookup_probe.
-constexpr int PMH_FLAG_LOOKUP = 1 << 15;
-
-// k_lookup_probe: for every row of the section's level-0 runs (probe_off[r]
-// >= 0: word offset of run r's first row; < 0: run r is not probed), the
-// packed (slot, row) of the first lookup level — slots k .. k+n_levels-1,
+// k_lookup_probe: for every row of the section's level-0 runs (ProbeSet::off),
+// the packed (slot, row) of the first lookup level — slots k .. n_slots - 1,
 // lowest level first — that holds the row's key, or 0xFFFFFFFF.
-hipError_t pmh_launch_lookup_probe(const DevCol *keys, const int64_t *lens,
-                                   const int64_t *probe_off, int k,
-                                   int n_levels, int64_t max_run_rows,
-                                   uint32_t *words, hipStream_t stream);
+hipError_t pmh_launch_lookup_probe(const RunSet &runs, const ProbeSet &probe,
+                                   hipStream_t stream);
 
 hipError_t pmh_launch_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
                                  int64_t *tile_offsets, int64_t *total_out,
@@ -215,39 +349,18 @@ hipError_t pmh_launch_scan_tiles(const int32_t *tile_counts, int64_t n_tiles,
 
 // FUSED merge + emit (deduplicate / first-row): ticket-ordered persistent
 // workgroups, decoupled-lookback output offsets (packed agent-scope atomic
-// per tile in `status`, zeroed before launch along with `ticket`), emission
-// from LDS-staged columns. Replaces merge_tiles + scan_tiles + emit for
-// non-member-list engines. key_col = -1 for composite keys (key columns
-// then emit through the generic column path).
-hipError_t pmh_launch_merge_emit(const DevCol *keys, const DevCol *seqs,
-                                 const DevCol *kinds, const int64_t *lens,
-                                 int k, const int32_t *cuts,
-                                 int64_t tile_base, int64_t tile_limit,
-                                 int64_t n_tiles,
-                                 int64_t tile_rows, int flags,
-                                 const uint64_t *tombs,
-                                 const DevCol *cols, const uint8_t *col_dtype,
-                                 const uint8_t *col_nullable, int n_cols,
-                                 int key_col, int seq_col, int kind_col,
-                                 const int16_t *useq_cols, int n_useq,
-                                 uint64_t *status, uint64_t *ticket,
-                                 int64_t *total_out, uint32_t *dense_winners,
-                                 void *const *out_ptrs,
-                                 uint8_t *const *out_valid,
-                                 uint32_t *err_flag, hipStream_t stream);
+// per tile in tiles.status, zeroed before launch along with tiles.ticket),
+// emission from LDS-staged columns. Replaces merge_tiles + scan_tiles + emit
+// for non-member-list engines; one launch covers tiles [0, n_tiles).
+hipError_t pmh_launch_merge_emit(const RunSet &runs, const ColumnSet &columns,
+                                 const TileSet &tiles, int flags,
+                                 const OutputSet &out, hipStream_t stream);
 
 // SPLIT-mode value emission: gathers value columns by the densely-written
-// packed winners (k_merge_emit with dense_winners != null emitted key/seq/
-// kind and the winner list; this kernel runs at full occupancy, no LDS).
-hipError_t pmh_launch_emit_dense(const DevCol *cols,
-                                 const uint8_t *col_dtype,
-                                 const uint8_t *col_nullable, int n_cols,
-                                 int key_col, int seq_col, int kind_col,
-                                 const uint32_t *winners,
-                                 int64_t t0, int64_t t1,
-                                 const uint64_t *status,
-                                 void *const *out_ptrs,
-                                 uint8_t *const *out_valid,
+// packed winners (k_merge_emit with tiles.dense_winners != null emitted key/
+// seq/kind and the winner list; this kernel runs at full occupancy, no LDS).
+hipError_t pmh_launch_emit_dense(const RunSet &runs, const ColumnSet &columns,
+                                 const TileSet &tiles, const OutputSet &out,
                                  hipStream_t stream);
 
 // The kernel the last pmh_launch_emit chose.
@@ -259,24 +372,15 @@ enum {
 };
 int pmh_last_emit_kernel();
 
-// Winner gather. n_desc = run slots of `cols` that a winner word can name
-// (the k merge runs plus a lookup plan's level slots). cuts / lens are the
-// partition's cuts ((n_tiles + 1) * k) and the k run lengths the winners
-// were merged from; any_nullable = some column of the plan has a validity
-// output. Plans without lookup slots (n_desc == k) and without nullable
-// columns stream their tile slices through LDS (k_emit_stream,
-// PMH_EMIT_STREAM=0 turns it off); other plans whose descriptor table fits
-// LDS run k_emit_contig; the rest, and PMH_EMIT_LEGACY=1, run k_emit, which
-// reads its descriptors from global memory.
-hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
-                           const uint8_t *col_nullable, int any_nullable,
-                           int n_cols, int k, int n_desc,
-                           const int32_t *cuts, const int64_t *lens,
-                           const uint32_t *winners,
-                           const int32_t *tile_counts,
-                           const int64_t *tile_offsets, int64_t n_tiles,
-                           int64_t tile_rows, const int64_t *total_out,
-                           void *const *out_ptrs, uint8_t *const *out_valid,
+// Winner gather. A winner word can name any of runs.n_slots run slots (the k
+// merge runs plus a lookup plan's level slots). Plans without lookup slots
+// (n_slots == k) and without nullable columns stream their tile slices
+// through LDS (k_emit_stream, PMH_EMIT_STREAM=0 turns it off); other plans
+// whose descriptor table fits LDS run k_emit_contig; the rest, and
+// PMH_EMIT_LEGACY=1, run k_emit, which reads its descriptors from global
+// memory.
+hipError_t pmh_launch_emit(const RunSet &runs, const ColumnSet &columns,
+                           const TileSet &tiles, const OutputSet &out,
                            hipStream_t stream);
 
 hipError_t pmh_launch_rle_decode(const RleChunk *chunks, int64_t n_chunks,
@@ -290,19 +394,11 @@ hipError_t pmh_launch_level_scatter(const RleChunk *chunks, int64_t n_chunks,
 
 // PartialUpdate emit: per owned group, overlay non-null fields in ascending
 // (seq, isAdd) order (PartialUpdateMergeFunction.java:188-215 + Reducer
-// wrapper bypass). members/group_start written by k_merge_tiles in PU mode.
-// run_masks: device array of k per-run packed-validity pointers
-// (k_pack_valid), or null for the legacy per-column byte walk (>64 cols).
-hipError_t pmh_launch_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
-                              const uint8_t *col_nullable, int n_cols, int k,
-                              int seq_col, int kind_col, int flags,
-                              const uint32_t *members,
-                              const uint16_t *group_start,
-                              const int64_t *tile_offsets, int64_t n_tiles,
-                              int64_t tile_rows, const int64_t *total_out,
-                              uint64_t *const *run_masks,
-                              void *const *out_ptrs,
-                              uint8_t *const *out_valid, hipStream_t stream);
+// wrapper bypass). Members / group_start written by k_merge_tiles under
+// PMH_FLAG_MEMBERS.
+hipError_t pmh_launch_emit_pu(const RunSet &runs, const ColumnSet &columns,
+                              const TileSet &tiles, int flags,
+                              const OutputSet &out, hipStream_t stream);
 
 // Pack one run's per-column validity bytes into u64 row masks (bit c =
 // column c non-null; columns without staged nulls contribute 1).
@@ -317,9 +413,9 @@ hipError_t pmh_launch_composite(const DevCol *keys, int nk, uint64_t shifts,
 
 // Aggregation emit: per owned group, fold members in ascending (seq, isAdd)
 // order through per-column FieldAggregators (AggregateMergeFunction.java:
-// 82-125; default last_non_null_value, :201). col_agg holds one PMH_AGG_*
+// 82-125; default last_non_null_value, :201). columns.agg holds one PMH_AGG_*
 // code per output column. INSERT-only streams in v1 (retracts are detected
-// by k_merge_tiles in PU mode and fail the read).
+// by k_merge_tiles in member-list mode and fail the read).
 enum {
     PMH_AGG_LAST_NON_NULL = 0,  // FieldLastNonNullValueAgg (the default)
     PMH_AGG_LAST_VALUE = 1,     // FieldLastValueAgg
@@ -335,34 +431,18 @@ enum {
 constexpr uint8_t PMH_AGG_IGNORE_RETRACT = 0x80;
 // PartialUpdate with sequence groups (PartialUpdateMergeFunction.java:
 // 219-377): per-group last-prefix-max-achiever resolution; retracts null
-// their group members. col_group[c] = group id or 0xff; sg_fields packs 4
-// sequence-field column indices per group; no per-field aggregators in v1.
-hipError_t pmh_launch_emit_pu_sg(
-    const DevCol *cols, const uint8_t *col_dtype,
-    const uint8_t *col_nullable, int n_cols, int k, int seq_col,
-    int kind_col, int flags, const uint8_t *col_group,
-    const int16_t *sg_fields, const uint8_t *sg_nseq, int n_groups,
-    const uint32_t *members, const uint16_t *group_start,
-    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
-    const int64_t *total_out, uint64_t *const *run_masks,
-    void *const *out_ptrs, uint8_t *const *out_valid, hipStream_t stream);
+// their group members (SeqGroupSet); no per-field aggregators in v1.
+hipError_t pmh_launch_emit_pu_sg(const RunSet &runs, const ColumnSet &columns,
+                                 const SeqGroupSet &groups,
+                                 const TileSet &tiles, int flags,
+                                 const OutputSet &out, hipStream_t stream);
 
-hipError_t pmh_launch_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
-                               const uint8_t *col_nullable,
-                               const uint8_t *col_agg, int n_cols, int k,
-                               int seq_col, int kind_col, int flags,
-                               const uint32_t *members,
-                               const uint16_t *group_start,
-                               const int64_t *tile_offsets, int64_t n_tiles,
-                               int64_t tile_rows, const int64_t *total_out,
-                               uint64_t *const *run_masks,
-                               void *const *out_ptrs,
-                               uint8_t *const *out_valid, hipStream_t stream);
+hipError_t pmh_launch_emit_agg(const RunSet &runs, const ColumnSet &columns,
+                               const TileSet &tiles, int flags,
+                               const OutputSet &out, hipStream_t stream);
 
 hipError_t pmh_launch_dict_gather(const int32_t *ids, const void *dict,
                                   int64_t n, void *out, int esize,
                                   hipStream_t stream);
-
-}  // extern "C"
 
 }  // namespace pmh

@@ -563,9 +563,8 @@ DEV void tile_prefetch(const TileSmem &sm, TileSetup &st,
 // Separate template instantiations keep the PU path's extra registers out
 // of the deduplicate kernel.
 //
-// LK=true: lookup changelog producer (flags bit PMH_FLAG_LOOKUP; bits 8..14
-// are the profiling knobs) — the winner walk
-// applies LookupMergeFunction's level rules and reads k_lookup_probe's
+// LK=true: lookup changelog producer (flags bit PMH_FLAG_LOOKUP) — the winner
+// walk applies LookupMergeFunction's level rules and reads k_lookup_probe's
 // per-row probe words; its own instantiation, so the other modes' code is
 // untouched.
 //
@@ -596,8 +595,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                    // keys/seqs/kinds then carry the lookup-level slots
                    // after the k merge runs
                    const uint32_t *probe_words, const int64_t *probe_off) {
-    const bool drop_delete = flags & 1;
-    const bool ignore_delete = flags & 2;
+    const bool drop_delete = flags & PMH_FLAG_DROP_DELETE;
+    const bool ignore_delete = flags & PMH_FLAG_IGNORE_DELETE;
     // FR = first-row engine (FirstRowMergeFunction.java:32-77): keep the
     // FIRST record per key in ascending (seq, isAdd) order; retracts throw
     // unless ignore-delete (then skipped); singleton groups bypass the merge
@@ -608,19 +607,20 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
     // legal; a group whose LAST member (max packed sseq) is a DELETE yields
     // a DELETE result and is dropped here under drop_delete. UPDATE_BEFORE
     // is rejected at staging (v1: INSERT/DELETE streams).
-    const bool rrod = (flags & 16) != 0;
+    const bool rrod = (flags & PMH_FLAG_RROD) != 0;
     // sequence groups (PartialUpdateMergeFunction.java:219-377): retracts
     // are legal members (they retract their groups); result kind is DELETE
     // only when the group has NO add member (getResult :389-397)
-    const bool seqg = (flags & 32) != 0;
+    const bool seqg = (flags & PMH_FLAG_SEQ_GROUPS) != 0;
     // aggregation with retract-capable aggregators (FieldSumAgg.retract /
     // FieldPrimaryKeyAgg / ignore-retract wrappers): retract members are
     // legal and fold through aggregator.retract in k_emit_agg
-    const bool aggr = (flags & 64) != 0;
-    // ablation levels (profiling only, flags bits 8..): 1=stage,2=+merge,
-    // 3=+scan, 0/absent=full. Partial levels publish a checksum so the
-    // compiler cannot dead-code the ablated phases' inputs.
-    const int ablate = (flags >> 8) & 0xf;
+    const bool aggr = (flags & PMH_FLAG_AGG_RETRACT) != 0;
+    // ablation levels (profiling only, the PMH_FLAG_ABLATE field): 1=stage,
+    // 2=+merge, 3=+scan, 0/absent=full. Partial levels publish a checksum so
+    // the compiler cannot dead-code the ablated phases' inputs.
+    const int ablate =
+        (flags >> PMH_FLAG_ABLATE_SHIFT) & PMH_FLAG_ABLATE_MASK;
     __shared__ TileSmem sm;
     const int tid = threadIdx.x;
     // the staged columns are contiguous: keep their bases in LDS, once
@@ -665,9 +665,9 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     const int32_t kd = rg.kind[s];
                     const bool dead = TOMBS && rg.tomb[TOMBS ? s : 0];
                     if (PU && rrod && !seqg && kd == 1 && !dead && err_flag)
-                        atomicOr(err_flag, 1u);  // UPDATE_BEFORE: not in v1
-                                                 // RROD (sequence groups
-                                                 // accept it)
+                        // UPDATE_BEFORE: not in v1 RROD (sequence groups
+                        // accept it)
+                        atomicOr(err_flag, PMH_ERR_RETRACT);
                     sm.skey[e] =
                         kes == 8 ? rg.key[s] : (int64_t)(int32_t)rg.key[s];
                     sm.sseq[e] = dead ? PMH_DEAD
@@ -878,14 +878,16 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                         // depend on drop-delete. merged = the wrapper's
                         // result; its kind follows the drop rules below.
                         if (n_top > 1 && err_flag)
-                            atomicOr(err_flag, 8u);  // checkState :76-78
+                            // checkState :76-78
+                            atomicOr(err_flag, PMH_ERR_TOP_LEVEL_DUP);
                         const bool m_add =
                             nlive == 1 ? ps2m_isadd(sm.sseq[live1])
                             : seqg     ? any_add
                             : rrod     ? ps2m_isadd(mx)
                                        : true;
                         const ClcDecision d = clc_decide(
-                            nlive, n_top, m_add, (flags & 128) != 0);
+                            nlive, n_top, m_add,
+                            (flags & PMH_FLAG_CL_ROW_DEDUP) != 0);
                         if (d.n) {
                             if (pass == 1) {
                                 const uint64_t pd =
@@ -1014,7 +1016,7 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                     m_off = addm + im - nm;
                 }
             }
-            if (bad_kind && err_flag) atomicOr(err_flag, 1u);
+            if (bad_kind && err_flag) atomicOr(err_flag, PMH_ERR_RETRACT);
             if (tid == 0) {
                 tile_counts[tile] = total_g;
                 gout[total_g] = (uint16_t)total_m;  // sentinel
@@ -1041,10 +1043,10 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
         // full-compaction changelog (FullChangelogMergeFunctionWrapper.java:
         // 96-126): per live group, up to two provisional entries, written
         // INDEPENDENTLY of drop-delete (a dropped DELETE result still emits
-        // DELETE(topLevelKv)). flags bit 128 = row-deduplicate pending
+        // DELETE(topLevelKv)). PMH_FLAG_CL_ROW_DEDUP = row-deduplicate pending
         // (k_cl_finalize compares values and may drop the UB/UA pair).
         const bool cl = cl_entries != nullptr;
-        const bool cl_pend = (flags & 128) != 0;
+        const bool cl_pend = (flags & PMH_FLAG_CL_ROW_DEDUP) != 0;
         uint64_t *clout =
             cl ? &cl_entries[tile * 2 * (tile_rows + PMH_MAX_RUNS)] : nullptr;
         // map seg index -> packed (run, global row)
@@ -1220,7 +1222,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 if (nlive == 0) continue;
                 if (cl) {
                     if (n_top > 1 && err_flag)
-                        atomicOr(err_flag, 8u);  // checkState :76-78
+                        // checkState :76-78
+                        atomicOr(err_flag, PMH_ERR_TOP_LEVEL_DUP);
                     // merged = wrapper result; singletons bypass the merge
                     // function (so an ignored lone record still serves)
                     bool m_ok = nlive == 1 || e_best;
@@ -1258,7 +1261,8 @@ void k_merge_tiles(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 }
                 if (first_row && !ignore_delete && any_retract && nlive > 1 &&
                     err_flag)
-                    atomicOr(err_flag, 2u);  // FirstRow rejects retracts
+                    // FirstRow rejects retracts
+                    atomicOr(err_flag, PMH_ERR_FIRST_ROW_RETRACT);
                 if (!e_best && nlive > 1) continue;  // all records ignored
                 if (drop_delete && !(v_best & 1)) continue;
                 if (one_walk) {
@@ -1398,8 +1402,8 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                   int64_t *total_out, uint32_t *dense_winners,
                   void *const *out_ptrs,
                   uint8_t *const *out_valid, uint32_t *err_flag) {
-    const bool drop_delete = flags & 1;
-    const bool ignore_delete = flags & 2;
+    const bool drop_delete = flags & PMH_FLAG_DROP_DELETE;
+    const bool ignore_delete = flags & PMH_FLAG_IGNORE_DELETE;
     __shared__ FusedSmem sm;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1478,7 +1482,7 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                 if (nlive == 0) continue;
                 if (FR && !ignore_delete && any_retract && nlive > 1 &&
                     err_flag)
-                    atomicOr(err_flag, 2u);
+                    atomicOr(err_flag, PMH_ERR_FIRST_ROW_RETRACT);
                 if (!e_best && nlive > 1) continue;
                 if (drop_delete && !ps2_isadd(v_best)) continue;
                 emit(nloc, s_best);
@@ -1726,7 +1730,7 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
                                                    __HIP_MEMORY_SCOPE_AGENT);
                         } while ((st >> 62) == 0 && ++spins < (1ll << 27));
                         if ((st >> 62) == 0) {  // bounded spin: fail loudly
-                            if (err_flag) atomicOr(err_flag, 4u);
+                            if (err_flag) atomicOr(err_flag, PMH_ERR_LOOKBACK);
                             st = LOOK_PREFIX;
                         }
                     }
@@ -1755,9 +1759,9 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
         __syncthreads();
         if (C == 0) continue;  // nothing to emit (all threads agree: C is
                                // uniform after the pass-0 block reduction)
-        const int ablate = (flags >> 12) & 0x3;  // profiling-only: 1 = skip
-                                                 // value loop, 2 = skip all
-                                                 // emission
+        // profiling-only: 1 = skip value loop, 2 = skip all emission
+        const int ablate =
+            (flags >> PMH_FLAG_FABL_SHIFT) & PMH_FLAG_FABL_MASK;
         if (ablate == 2) continue;
         const int64_t goff = sm.s_goff;
         // staged keys may be 32-bit tile-relative: reconstruct the original
@@ -1861,13 +1865,14 @@ void k_merge_emit(const DevCol *keys, const DevCol *seqs, const DevCol *kinds,
         bool any_null = false;
         for (int c = 0; c < n_cols; c++)
             if (col_nullable[c]) any_null = true;
-        // emission mode (flags bit 14): 0 = direct gather per winner (high
-        // MLP, no per-column barriers — winners are ~72% dense within their
-        // run segments, so the 64B gather lines are mostly reused and the
-        // working set stays XCD-L2-resident); 1 = LDS-staged columns
+        // emission mode (the PMH_FLAG_FSTAGE field): 0 = direct gather per
+        // winner (high MLP, no per-column barriers — winners are ~72% dense
+        // within their run segments, so the 64B gather lines are mostly reused
+        // and the working set stays XCD-L2-resident); 1 = LDS-staged columns
         // (coalesced loads but burst-and-wait per column: measured slower,
         // kept for A/B via PMH_FSTAGE)
-        const bool staged = (flags >> 14) & 1;
+        const bool staged =
+            (flags >> PMH_FLAG_FSTAGE_SHIFT) & PMH_FLAG_FSTAGE_MASK;
 
         // --- overlap window 1: first column's gathers fly while the
         // key/seq/kind emit reads the merge arrays
@@ -2899,13 +2904,13 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
                           int64_t tile_rows, const int64_t *total_out,
                           uint64_t *const *run_masks, void *const *out_ptrs,
                           uint8_t *const *out_valid) {
-    // remove-record-on-delete (flags bit 16): a DELETE resets the row —
+    // remove-record-on-delete (PMH_FLAG_RROD): a DELETE resets the row —
     // per column, overlay only the adds NEWER than the last DELETE and fall
     // back to the DELETE record's own field (initRow semantics,
     // PartialUpdateMergeFunction.java:173-180). Result kind = DELETE when
     // the last member is the DELETE (getResult, :213-221). Groups whose result
     // DELETE were already dropped by the merge pass under drop_delete.
-    const bool rrod = (flags & 16) != 0;
+    const bool rrod = (flags & PMH_FLAG_RROD) != 0;
     const int64_t total = *total_out;
     const int64_t slice_lo = slice_lo_of(total);
     const int64_t slice_hi = slice_hi_of(total);
@@ -3045,7 +3050,7 @@ __global__ void k_emit_pu_sg(const DevCol *cols, const uint8_t *col_dtype,
                              uint64_t *const *run_masks,
                              void *const *out_ptrs,
                              uint8_t *const *out_valid) {
-    const bool ignore_delete = flags & 2;
+    const bool ignore_delete = flags & PMH_FLAG_IGNORE_DELETE;
     const int64_t total = *total_out;
     const int64_t slice_lo = slice_lo_of(total);
     const int64_t slice_hi = slice_hi_of(total);
@@ -3230,12 +3235,12 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                            int64_t tile_rows, const int64_t *total_out,
                            uint64_t *const *run_masks, void *const *out_ptrs,
                            uint8_t *const *out_valid) {
-    // remove-record-on-delete (flags bit 16): a DELETE re-initializes the
+    // remove-record-on-delete (PMH_FLAG_RROD): a DELETE re-initializes the
     // row from its own value and the aggregators continue FROM those values
     // (AggregateMergeFunction.add, currentDeleteRow path) — so folds seed
     // with the last DELETE's field and consume only newer adds. first_*
     // aggregators are rejected at plan creation under this mode.
-    const bool rrod = (flags & 16) != 0;
+    const bool rrod = (flags & PMH_FLAG_RROD) != 0;
     auto kind_of = [&](uint32_t m) -> int32_t {
         return col_load<int32_t>(member_col(cols, n_cols, m, kind_col),
                                  member_row(m));
@@ -3308,10 +3313,10 @@ __global__ void k_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
                 if (MASKS) vdel = member_mask(run_masks, mdel);
             }
         }
-        // retract mode (flags bit 64): per-member kinds drive
+        // retract mode (PMH_FLAG_AGG_RETRACT): per-member kinds drive
         // aggregator.retract; only reached when every column's aggregator
         // is retract-capable (plan validation)
-        const bool aggr = (flags & 64) != 0;
+        const bool aggr = (flags & PMH_FLAG_AGG_RETRACT) != 0;
         for (int c = 0; c < n_cols; c++) {
             if (c == kind_col) {
                 // wrapper bypass: singletons keep their own RowKind
@@ -5074,9 +5079,8 @@ static int emit_grid() {
 }
 
 // ---------------------------------------------------------------- launchers
-
-
-extern "C" {
+// Each unpacks its argument structs (kernels.h) into its kernel's argument
+// list; tiles are PMH_TILE_ROWS rows everywhere but in pmh_launch_partition.
 
 hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
                                 int64_t tile_rows, int64_t n_bounds,
@@ -5134,18 +5138,9 @@ hipError_t pmh_launch_partition(const DevCol *keys, const int64_t *lens, int k,
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
-                                  const DevCol *kinds, const int64_t *lens,
-                                  int k, const int32_t *cuts, int64_t n_tiles,
-                                  int64_t tile_rows, int flags,
-                                  const uint64_t *tombs,
-                                  uint32_t *winners, int32_t *tile_counts,
-                                  uint16_t *group_start, uint32_t *err_flag,
-                                  const uint8_t *run_levels, int max_level,
-                                  uint64_t *cl_entries, int32_t *cl_counts,
-                                  const uint32_t *probe_words,
-                                  const int64_t *probe_off,
-                                  hipStream_t stream) {
+hipError_t pmh_launch_merge_tiles(const RunSet &runs, const TileSet &tiles,
+                                  int flags, const ChangelogSet &cl,
+                                  const ProbeSet &probe, hipStream_t stream) {
     // A block pipelines its staging across its tiles, but fewer, longer-lived
     // blocks did not pay: 512 / 1024 / 2048 / 4096 blocks measured 1.47 /
     // 1.47 / 1.45 / 1.44 ms at 8 x 10M rows and 7.33 / 7.34 / 7.29 / 7.05 ms
@@ -5158,15 +5153,19 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
         const long long v = atoll(e);
         if (v >= 1 && v <= 65535) max_blocks = v;
     }
-    int blocks = n_tiles < max_blocks ? (int)n_tiles : (int)max_blocks;
-    const bool pu = flags & 4, fr = flags & 8,
+    const int k = runs.k;
+    int blocks =
+        tiles.n_tiles < max_blocks ? (int)tiles.n_tiles : (int)max_blocks;
+    const bool pu = flags & PMH_FLAG_MEMBERS, fr = flags & PMH_FLAG_FIRST_ROW,
                lk = flags & PMH_FLAG_LOOKUP;
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(PMH_TILE_THREADS), 0,
-                           stream, keys, seqs, kinds, lens, k, cuts, n_tiles,
-                           tile_rows, flags, tombs, winners, tile_counts,
-                           group_start, err_flag, run_levels, max_level,
-                           cl_entries, cl_counts, probe_words, probe_off);
+                           stream, runs.keys, runs.seqs, runs.kinds,
+                           runs.lens, k, tiles.cuts, tiles.n_tiles,
+                           PMH_TILE_ROWS, flags, runs.tombs, tiles.winners,
+                           tiles.counts, tiles.group_start, tiles.err,
+                           runs.levels, cl.max_level, cl.entries, cl.counts,
+                           probe.words, probe.off);
     };
     // KM = unrolled run bound of the staging setup (k_partition_wave's)
     // and TOMBS = deletion-vector bytes ride along (their registers stay out
@@ -5195,35 +5194,29 @@ hipError_t pmh_launch_merge_tiles(const DevCol *keys, const DevCol *seqs,
         else
             launch_km(std::integral_constant<int, PMH_MAX_RUNS>{}, tb);
     };
-    if (tombs)
+    if (runs.tombs)
         launch_k(std::true_type{});
     else
         launch_k(std::false_type{});
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
-                              const uint8_t *col_nullable, int n_cols, int k,
-                              int seq_col, int kind_col, int flags,
-                              const uint32_t *members,
-                              const uint16_t *group_start,
-                              const int64_t *tile_offsets, int64_t n_tiles,
-                              int64_t tile_rows, const int64_t *total_out,
-                              uint64_t *const *run_masks,
-                              void *const *out_ptrs,
-                              uint8_t *const *out_valid, hipStream_t stream) {
-    if (run_masks)
-        hipLaunchKernelGGL(k_emit_pu<true>, dim3(emit_grid()), dim3(256), 0, stream,
-                           cols, col_dtype, col_nullable, n_cols, k, seq_col,
-                           kind_col, flags, members, group_start,
-                           tile_offsets, n_tiles, tile_rows, total_out,
-                           run_masks, out_ptrs, out_valid);
+hipError_t pmh_launch_emit_pu(const RunSet &runs, const ColumnSet &columns,
+                              const TileSet &tiles, int flags,
+                              const OutputSet &out, hipStream_t stream) {
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(emit_grid()), dim3(256), 0, stream,
+                           runs.cols, columns.dtype, columns.nullable,
+                           columns.n_cols, runs.k, columns.seq_col(),
+                           columns.kind_col(), flags, tiles.winners,
+                           tiles.group_start, tiles.offsets, tiles.n_tiles,
+                           PMH_TILE_ROWS, tiles.total, runs.masks, out.ptrs,
+                           out.valid);
+    };
+    if (runs.masks)
+        launch(k_emit_pu<true>);
     else
-        hipLaunchKernelGGL(k_emit_pu<false>, dim3(emit_grid()), dim3(256), 0, stream,
-                           cols, col_dtype, col_nullable, n_cols, k, seq_col,
-                           kind_col, flags, members, group_start,
-                           tile_offsets, n_tiles, tile_rows, total_out,
-                           run_masks, out_ptrs, out_valid);
+        launch(k_emit_pu<false>);
     return hipGetLastError();
 }
 
@@ -5242,89 +5235,69 @@ hipError_t pmh_launch_pack_valid(const DevCol *cols, int n_cols, int64_t rows,
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_emit_pu_sg(
-    const DevCol *cols, const uint8_t *col_dtype,
-    const uint8_t *col_nullable, int n_cols, int k, int seq_col,
-    int kind_col, int flags, const uint8_t *col_group,
-    const int16_t *sg_fields, const uint8_t *sg_nseq, int n_groups,
-    const uint32_t *members, const uint16_t *group_start,
-    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
-    const int64_t *total_out, uint64_t *const *run_masks,
-    void *const *out_ptrs, uint8_t *const *out_valid, hipStream_t stream) {
-    hipLaunchKernelGGL(k_emit_pu_sg, dim3(emit_grid()), dim3(256), 0, stream, cols,
-                       col_dtype, col_nullable, n_cols, k, seq_col, kind_col,
-                       flags, col_group, sg_fields, sg_nseq, n_groups,
-                       members, group_start, tile_offsets, n_tiles,
-                       tile_rows, total_out, run_masks, out_ptrs, out_valid);
+hipError_t pmh_launch_emit_pu_sg(const RunSet &runs, const ColumnSet &columns,
+                                 const SeqGroupSet &groups,
+                                 const TileSet &tiles, int flags,
+                                 const OutputSet &out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_emit_pu_sg, dim3(emit_grid()), dim3(256), 0, stream,
+                       runs.cols, columns.dtype, columns.nullable,
+                       columns.n_cols, runs.k, columns.seq_col(),
+                       columns.kind_col(), flags, groups.col_group,
+                       groups.fields, groups.nseq, groups.n_groups,
+                       tiles.winners, tiles.group_start, tiles.offsets,
+                       tiles.n_tiles, PMH_TILE_ROWS, tiles.total, runs.masks,
+                       out.ptrs, out.valid);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_emit_agg(const DevCol *cols, const uint8_t *col_dtype,
-                               const uint8_t *col_nullable,
-                               const uint8_t *col_agg, int n_cols, int k,
-                               int seq_col, int kind_col, int flags,
-                               const uint32_t *members,
-                               const uint16_t *group_start,
-                               const int64_t *tile_offsets, int64_t n_tiles,
-                               int64_t tile_rows, const int64_t *total_out,
-                               uint64_t *const *run_masks,
-                               void *const *out_ptrs,
-                               uint8_t *const *out_valid,
-                               hipStream_t stream) {
-    if (run_masks)
-        hipLaunchKernelGGL(k_emit_agg<true>, dim3(emit_grid()), dim3(256), 0, stream,
-                           cols, col_dtype, col_nullable, col_agg, n_cols, k,
-                           seq_col, kind_col, flags, members, group_start,
-                           tile_offsets, n_tiles, tile_rows, total_out,
-                           run_masks, out_ptrs, out_valid);
+hipError_t pmh_launch_emit_agg(const RunSet &runs, const ColumnSet &columns,
+                               const TileSet &tiles, int flags,
+                               const OutputSet &out, hipStream_t stream) {
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(emit_grid()), dim3(256), 0, stream,
+                           runs.cols, columns.dtype, columns.nullable,
+                           columns.agg, columns.n_cols, runs.k,
+                           columns.seq_col(), columns.kind_col(), flags,
+                           tiles.winners, tiles.group_start, tiles.offsets,
+                           tiles.n_tiles, PMH_TILE_ROWS, tiles.total,
+                           runs.masks, out.ptrs, out.valid);
+    };
+    if (runs.masks)
+        launch(k_emit_agg<true>);
     else
-        hipLaunchKernelGGL(k_emit_agg<false>, dim3(emit_grid()), dim3(256), 0,
-                           stream, cols, col_dtype, col_nullable, col_agg,
-                           n_cols, k, seq_col, kind_col, flags, members,
-                           group_start, tile_offsets, n_tiles, tile_rows,
-                           total_out, run_masks, out_ptrs, out_valid);
+        launch(k_emit_agg<false>);
     return hipGetLastError();
 }
 
 hipError_t pmh_launch_level_scatter(const RleChunk *chunks, int64_t n_chunks,
                                     hipStream_t stream) {
-    int blocks = n_chunks < 4096 ? (int)(n_chunks ? n_chunks : 1) : 4096;
+    int blocks = pmh_grid(n_chunks);
     hipLaunchKernelGGL(k_level_scatter, dim3(blocks), dim3(PMH_TILE_THREADS),
                        0, stream, chunks, n_chunks);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_merge_emit(const DevCol *keys, const DevCol *seqs,
-                                 const DevCol *kinds, const int64_t *lens,
-                                 int k, const int32_t *cuts,
-                                 int64_t tile_base, int64_t tile_limit,
-                                 int64_t n_tiles,
-                                 int64_t tile_rows, int flags,
-                                 const uint64_t *tombs,
-                                 const DevCol *cols, const uint8_t *col_dtype,
-                                 const uint8_t *col_nullable, int n_cols,
-                                 int key_col, int seq_col, int kind_col,
-                                 const int16_t *useq_cols, int n_useq,
-                                 uint64_t *status, uint64_t *ticket,
-                                 int64_t *total_out, uint32_t *dense_winners,
-                                 void *const *out_ptrs,
-                                 uint8_t *const *out_valid,
-                                 uint32_t *err_flag, hipStream_t stream) {
+hipError_t pmh_launch_merge_emit(const RunSet &runs, const ColumnSet &columns,
+                                 const TileSet &tiles, int flags,
+                                 const OutputSet &out, hipStream_t stream) {
     // persistent workgroups: 2 resident per CU (LDS-bound) x 256 CUs; the
-    // ticket (zeroed before this launch) hands out the chunk's tiles in
-    // order, so any residency is safe
-    const int64_t chunk = tile_limit - tile_base;
-    int blocks = chunk < 512 ? (int)chunk : 512;
-    const bool fr = flags & 8;
+    // ticket (zeroed before this launch) hands out the tiles in order, so
+    // any residency is safe
+    const int64_t n_tiles = tiles.n_tiles;
+    int blocks = n_tiles < 512 ? (int)n_tiles : 512;
+    const bool fr = flags & PMH_FLAG_FIRST_ROW;
     auto launch = [&](auto kern) {
+        // tile_base / tile_limit: the whole tile space in one launch
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(PMH_TILE_THREADS), 0,
-                           stream, keys, seqs, kinds, lens, k, cuts,
-                           tile_base, tile_limit, n_tiles, tile_rows, flags,
-                           tombs, cols, col_dtype, col_nullable,
-                           n_cols, key_col, seq_col, kind_col, useq_cols,
-                           n_useq, status, ticket,
-                           total_out, dense_winners, out_ptrs, out_valid,
-                           err_flag);
+                           stream, runs.keys, runs.seqs, runs.kinds,
+                           runs.lens, runs.k, tiles.cuts, (int64_t)0, n_tiles,
+                           n_tiles, PMH_TILE_ROWS, flags, runs.tombs,
+                           runs.cols, columns.dtype, columns.nullable,
+                           columns.n_cols, columns.key_col(),
+                           columns.seq_col(), columns.kind_col(),
+                           columns.useq, columns.n_useq, tiles.status,
+                           tiles.ticket, tiles.total, tiles.dense_winners,
+                           out.ptrs, out.valid, tiles.err);
     };
     if (fr)
         launch(k_merge_emit<true>);
@@ -5333,20 +5306,15 @@ hipError_t pmh_launch_merge_emit(const DevCol *keys, const DevCol *seqs,
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_emit_dense(const DevCol *cols,
-                                 const uint8_t *col_dtype,
-                                 const uint8_t *col_nullable, int n_cols,
-                                 int key_col, int seq_col, int kind_col,
-                                 const uint32_t *winners,
-                                 int64_t t0, int64_t t1,
-                                 const uint64_t *status,
-                                 void *const *out_ptrs,
-                                 uint8_t *const *out_valid,
+hipError_t pmh_launch_emit_dense(const RunSet &runs, const ColumnSet &columns,
+                                 const TileSet &tiles, const OutputSet &out,
                                  hipStream_t stream) {
-    hipLaunchKernelGGL(k_emit_dense, dim3(emit_grid()), dim3(256), 0, stream, cols,
-                       col_dtype, col_nullable, n_cols, key_col, seq_col,
-                       kind_col, winners, t0, t1, status, out_ptrs,
-                       out_valid);
+    // t0 / t1: the whole tile space
+    hipLaunchKernelGGL(k_emit_dense, dim3(emit_grid()), dim3(256), 0, stream,
+                       runs.cols, columns.dtype, columns.nullable,
+                       columns.n_cols, columns.key_col(), columns.seq_col(),
+                       columns.kind_col(), tiles.dense_winners, (int64_t)0,
+                       tiles.n_tiles, tiles.status, out.ptrs, out.valid);
     return hipGetLastError();
 }
 
@@ -5372,16 +5340,11 @@ int pmh_last_emit_kernel() { return g_last_emit_kernel; }
 //  - k_emit_contig (descriptors in LDS) for the other plans whose tables fit;
 //  - k_emit (descriptors read from global memory) for the rest, such as 32
 //    runs x 32 columns, and under PMH_EMIT_LEGACY=1.
-hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
-                           const uint8_t *col_nullable, int any_nullable,
-                           int n_cols, int k, int n_desc,
-                           const int32_t *cuts, const int64_t *lens,
-                           const uint32_t *winners,
-                           const int32_t *tile_counts,
-                           const int64_t *tile_offsets, int64_t n_tiles,
-                           int64_t tile_rows, const int64_t *total_out,
-                           void *const *out_ptrs, uint8_t *const *out_valid,
+hipError_t pmh_launch_emit(const RunSet &runs, const ColumnSet &columns,
+                           const TileSet &tiles, const OutputSet &out,
                            hipStream_t stream) {
+    const int k = runs.k, n_desc = runs.n_slots, n_cols = columns.n_cols;
+    const int64_t n_tiles = tiles.n_tiles;
     // Every knob is read per launch (tests vary them within a process).
     // R = rows per thread iteration, G = 4-byte columns per gather group
     // (8-byte columns go G / 2 at a time). PMH_EMIT_R sweeps 2/4 (legacy
@@ -5406,9 +5369,8 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
     const bool contig = n_desc >= 1 && n_cols <= 256 && lds <= EMIT_LDS_MAX &&
                         env_int("PMH_EMIT_LEGACY", 0) == 0;
     const int64_t tables = emit_stream_tables(k, n_cols);
-    const bool streamed = contig && n_desc == k && !any_nullable &&
-                          tables <= EMIT_LDS_MAX && cuts && lens &&
-                          tile_rows == PMH_TILE_ROWS &&
+    const bool streamed = contig && n_desc == k && !columns.any_nullable &&
+                          tables <= EMIT_LDS_MAX && tiles.cuts && runs.lens &&
                           env_int("PMH_EMIT_STREAM", 1) != 0;
     if (streamed) {
         // PMH_EMIT_STREAM_LDS: data bytes per block. It sets the columns per
@@ -5432,9 +5394,10 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
         const size_t bytes = (size_t)(tables + budget);
         auto launch = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(EMS_THREADS), bytes,
-                               stream, cols, col_dtype, n_cols, n_emit, k,
-                               cuts, lens, winners, tile_counts, tile_offsets,
-                               n_tiles, tile_rows, out_ptrs, (int)budget);
+                               stream, runs.cols, columns.dtype, n_cols,
+                               n_emit, k, tiles.cuts, runs.lens,
+                               tiles.winners, tiles.counts, tiles.offsets,
+                               n_tiles, PMH_TILE_ROWS, out.ptrs, (int)budget);
         };
         auto launch_g = [&](auto km) {
             constexpr int KM = decltype(km)::value;
@@ -5451,9 +5414,11 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
     if (contig) {
         auto launch = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(EMIT_THREADS), (size_t)lds,
-                               stream, cols, col_dtype, col_nullable, n_cols,
-                               n_emit, n_desc, winners, tile_offsets, n_tiles,
-                               tile_rows, total_out, out_ptrs, out_valid);
+                               stream, runs.cols, columns.dtype,
+                               columns.nullable, n_cols, n_emit, n_desc,
+                               tiles.winners, tiles.offsets, n_tiles,
+                               PMH_TILE_ROWS, tiles.total, out.ptrs,
+                               out.valid);
         };
         if (r_rows == 2) {
             if (g_cols == 2) launch(k_emit_contig<2, 2, 1>);
@@ -5468,10 +5433,11 @@ hipError_t pmh_launch_emit(const DevCol *cols, const uint8_t *col_dtype,
         return hipGetLastError();
     }
     auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, cols,
-                           col_dtype, col_nullable, n_cols, n_emit, k,
-                           winners, tile_counts, tile_offsets, n_tiles,
-                           tile_rows, total_out, out_ptrs, out_valid);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, runs.cols,
+                           columns.dtype, columns.nullable, n_cols, n_emit, k,
+                           tiles.winners, tiles.counts, tiles.offsets,
+                           n_tiles, PMH_TILE_ROWS, tiles.total, out.ptrs,
+                           out.valid);
     };
     if (r_rows == 6)
         launch(k_emit<6>);
@@ -5489,88 +5455,76 @@ hipError_t pmh_launch_filter(const DevCol *cols, int n_cols,
                              int64_t rows, uint8_t *tomb,
                              hipStream_t stream) {
     int64_t want = (rows + 255) / 256;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_filter, dim3(blocks), dim3(256), 0, stream, cols,
                        n_cols, terms, n_terms, rows, tomb);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_lookup_probe(const DevCol *keys, const int64_t *lens,
-                                   const int64_t *probe_off, int k,
-                                   int n_levels, int64_t max_run_rows,
-                                   uint32_t *words, hipStream_t stream) {
-    if (k <= 0 || max_run_rows <= 0) return hipSuccess;
-    int64_t chunks = (max_run_rows + PLK_CHUNK - 1) / PLK_CHUNK;
-    int gx = chunks < 2048 ? (int)chunks : 2048;
-    hipLaunchKernelGGL(k_lookup_probe, dim3(gx, k), dim3(256), 0, stream,
-                       keys, lens, probe_off, k, n_levels, words);
+hipError_t pmh_launch_lookup_probe(const RunSet &runs, const ProbeSet &probe,
+                                   hipStream_t stream) {
+    if (runs.k <= 0 || probe.max_rows <= 0) return hipSuccess;
+    int64_t chunks = (probe.max_rows + PLK_CHUNK - 1) / PLK_CHUNK;
+    hipLaunchKernelGGL(k_lookup_probe, dim3(pmh_grid(chunks, 2048), runs.k),
+                       dim3(256), 0, stream, runs.keys, runs.lens, probe.off,
+                       runs.k, probe.n_levels, probe.words);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_cl_finalize(const DevCol *cols,
-                                  const uint8_t *col_dtype, int n_cols,
-                                  int first_val, int k,
-                                  const uint64_t *cl_entries,
-                                  uint64_t *cl_out, int32_t *cl_counts,
-                                  int64_t n_tiles, int64_t tile_rows,
+hipError_t pmh_launch_cl_finalize(const RunSet &runs, const ColumnSet &columns,
+                                  const TileSet &tiles, const ChangelogSet &cl,
                                   hipStream_t stream) {
-    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
-    hipLaunchKernelGGL(k_cl_finalize, dim3(blocks), dim3(256), 0, stream,
-                       cols, col_dtype, n_cols, first_val, k, cl_entries,
-                       cl_out, cl_counts, n_tiles, tile_rows);
+    hipLaunchKernelGGL(k_cl_finalize, dim3(pmh_grid(tiles.n_tiles)),
+                       dim3(256), 0, stream, runs.cols, columns.dtype,
+                       columns.n_cols, columns.first_val(), runs.k,
+                       cl.entries, cl.rows, cl.counts, tiles.n_tiles,
+                       PMH_TILE_ROWS);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_cl_emit(const DevCol *cols, const uint8_t *col_dtype,
-                              const uint8_t *col_nullable, int n_cols,
-                              int kind_col, const uint64_t *cl_rows,
-                              const int32_t *cl_counts,
-                              const int64_t *cl_offsets, int64_t n_tiles,
-                              int64_t tile_rows, void *const *out_ptrs,
-                              uint8_t *const *out_valid,
-                              hipStream_t stream) {
-    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
-    hipLaunchKernelGGL(k_cl_emit, dim3(blocks), dim3(256), 0, stream, cols,
-                       col_dtype, col_nullable, n_cols, kind_col, cl_rows,
-                       cl_counts, cl_offsets, n_tiles, tile_rows, out_ptrs,
-                       out_valid);
+hipError_t pmh_launch_cl_emit(const RunSet &runs, const ColumnSet &columns,
+                              const TileSet &tiles, const ChangelogSet &cl,
+                              const OutputSet &out2, hipStream_t stream) {
+    hipLaunchKernelGGL(k_cl_emit, dim3(pmh_grid(tiles.n_tiles)), dim3(256), 0,
+                       stream, runs.cols, columns.dtype, columns.nullable,
+                       columns.n_cols, columns.kind_col(), cl.rows, cl.counts,
+                       cl.offsets, tiles.n_tiles, PMH_TILE_ROWS, out2.ptrs,
+                       out2.valid);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_cl_finalize_out(
-    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
-    int n_cols, int first_val, int k, const uint64_t *cl_entries,
-    uint64_t *cl_out, int32_t *cl_counts, const int64_t *tile_offsets,
-    int64_t n_tiles, int64_t tile_rows, void *const *out_ptrs,
-    uint8_t *const *out_valid, hipStream_t stream) {
-    const int64_t lds = pmh_fold_cl_lds(k, n_cols);
+hipError_t pmh_launch_cl_finalize_out(const RunSet &runs,
+                                      const ColumnSet &columns,
+                                      const TileSet &tiles,
+                                      const ChangelogSet &cl,
+                                      const OutputSet &out,
+                                      hipStream_t stream) {
+    const int64_t lds = pmh_fold_cl_lds(runs.k, columns.n_cols);
     // a thread keeps its pairs' verdicts in one 32-bit register
-    if (lds > PMH_FOLD_CL_LDS_MAX ||
-        tile_rows + PMH_MAX_RUNS > 16 * FOLD_CL_THREADS)
-        return hipErrorInvalidValue;
-    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
-    hipLaunchKernelGGL(k_cl_finalize_out, dim3(blocks), dim3(FOLD_CL_THREADS),
-                       (size_t)lds, stream, cols, col_dtype, col_nullable,
-                       n_cols, first_val, k, cl_entries, cl_out, cl_counts,
-                       tile_offsets, n_tiles, tile_rows, out_ptrs, out_valid);
+    static_assert(PMH_TILE_ROWS + PMH_MAX_RUNS <= 16 * FOLD_CL_THREADS,
+                  "k_cl_finalize_out: 16 pairs per thread");
+    if (lds > PMH_FOLD_CL_LDS_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cl_finalize_out, dim3(pmh_grid(tiles.n_tiles)),
+                       dim3(FOLD_CL_THREADS), (size_t)lds, stream, runs.cols,
+                       columns.dtype, columns.nullable, columns.n_cols,
+                       columns.first_val(), runs.k, cl.entries, cl.rows,
+                       cl.counts, tiles.offsets, tiles.n_tiles, PMH_TILE_ROWS,
+                       out.ptrs, out.valid);
     return hipGetLastError();
 }
 
-hipError_t pmh_launch_cl_emit_out(
-    const DevCol *cols, const uint8_t *col_dtype, const uint8_t *col_nullable,
-    int n_cols, int k, int kind_col, const uint64_t *cl_rows,
-    const int32_t *cl_counts, const int64_t *cl_offsets,
-    const int64_t *tile_offsets, int64_t n_tiles, int64_t tile_rows,
-    void *const *out_ptrs, uint8_t *const *out_valid, void *const *out_ptrs2,
-    uint8_t *const *out_valid2, hipStream_t stream) {
-    const int64_t lds = pmh_fold_cl_lds(k, n_cols);
+hipError_t pmh_launch_cl_emit_out(const RunSet &runs, const ColumnSet &columns,
+                                  const TileSet &tiles, const ChangelogSet &cl,
+                                  const OutputSet &out, const OutputSet &out2,
+                                  hipStream_t stream) {
+    const int64_t lds = pmh_fold_cl_lds(runs.k, columns.n_cols);
     if (lds > PMH_FOLD_CL_LDS_MAX) return hipErrorInvalidValue;
-    int blocks = n_tiles < 4096 ? (int)n_tiles : 4096;
-    hipLaunchKernelGGL(k_cl_emit_out, dim3(blocks), dim3(FOLD_CL_THREADS),
-                       (size_t)lds, stream, cols, col_dtype, col_nullable,
-                       n_cols, k, kind_col, cl_rows, cl_counts, cl_offsets,
-                       tile_offsets, n_tiles, tile_rows, out_ptrs, out_valid,
-                       out_ptrs2, out_valid2);
+    hipLaunchKernelGGL(k_cl_emit_out, dim3(pmh_grid(tiles.n_tiles)),
+                       dim3(FOLD_CL_THREADS), (size_t)lds, stream, runs.cols,
+                       columns.dtype, columns.nullable, columns.n_cols, runs.k,
+                       columns.kind_col(), cl.rows, cl.counts, cl.offsets,
+                       tiles.offsets, tiles.n_tiles, PMH_TILE_ROWS, out.ptrs,
+                       out.valid, out2.ptrs, out2.valid);
     return hipGetLastError();
 }
 
@@ -5579,7 +5533,7 @@ hipError_t pmh_launch_zstd_compress(const uint8_t *src,
                                     uint8_t *dst, uint8_t *scratch,
                                     int64_t *status, hipStream_t stream) {
     int want = (n + 3) / 4;
-    int blocks = want < 4096 ? (want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_zstd_compress, dim3(blocks), dim3(256), 0, stream,
                        src, jobs, n, dst, scratch, status);
     return hipGetLastError();
@@ -5589,7 +5543,7 @@ hipError_t pmh_launch_zstd_pages(const uint8_t *src, const ZstdJob *jobs,
                                  int n, uint8_t *dst, uint8_t *scratch,
                                  int64_t *status, hipStream_t stream) {
     int want = (n + 3) / 4;  // 4 waves (pages) per 256-thread block
-    int blocks = want < 4096 ? (want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_zstd_pages, dim3(blocks), dim3(256), 0, stream, src,
                        jobs, n, dst, scratch, status);
     return hipGetLastError();
@@ -5599,7 +5553,7 @@ hipError_t pmh_launch_rlev2(const Rlev2Chunk *chunks, int64_t n_chunks,
                             hipStream_t stream) {
     int waves_per_block = 4;  // 256 threads
     int64_t want = (n_chunks + waves_per_block - 1) / waves_per_block;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_rlev2, dim3(blocks), dim3(256), 0, stream, chunks,
                        n_chunks);
     return hipGetLastError();
@@ -5610,7 +5564,7 @@ hipError_t pmh_launch_orc_varint(const VarintUnit *units, int64_t n_units,
                                  hipStream_t stream) {
     int waves_per_block = 4;  // 256 threads
     int64_t want = (n_units + waves_per_block - 1) / waves_per_block;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_orc_varint, dim3(blocks), dim3(256), 0, stream,
                        units, n_units);
     return hipGetLastError();
@@ -5620,7 +5574,7 @@ hipError_t pmh_launch_bits_expand(const BitsUnit *units, int64_t n_units,
                                   hipStream_t stream) {
     int waves_per_block = 4;  // 256 threads
     int64_t want = (n_units + waves_per_block - 1) / waves_per_block;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_bits_expand, dim3(blocks), dim3(256), 0, stream,
                        units, n_units);
     return hipGetLastError();
@@ -5628,7 +5582,7 @@ hipError_t pmh_launch_bits_expand(const BitsUnit *units, int64_t n_units,
 
 hipError_t pmh_launch_orc_timestamp(const TsUnit *units, int64_t n_units,
                                     hipStream_t stream) {
-    int blocks = n_units < 4096 ? (int)(n_units ? n_units : 1) : 4096;
+    int blocks = pmh_grid(n_units);
     hipLaunchKernelGGL(k_orc_timestamp, dim3(blocks), dim3(256), 0, stream,
                        units, n_units);
     return hipGetLastError();
@@ -5637,7 +5591,7 @@ hipError_t pmh_launch_orc_timestamp(const TsUnit *units, int64_t n_units,
 hipError_t pmh_launch_delta_sum(const DeltaChunk *chunks, int64_t n_chunks,
                                 int64_t *sums, hipStream_t stream) {
     int64_t want = (n_chunks + 3) / 4;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_delta_sum, dim3(blocks), dim3(256), 0, stream,
                        chunks, n_chunks, sums);
     return hipGetLastError();
@@ -5646,7 +5600,7 @@ hipError_t pmh_launch_delta_sum(const DeltaChunk *chunks, int64_t n_chunks,
 hipError_t pmh_launch_delta_scan(const DeltaStream *streams,
                                  int64_t n_streams, const int64_t *sums,
                                  int64_t *bases, hipStream_t stream) {
-    int blocks = n_streams < 2048 ? (int)(n_streams ? n_streams : 1) : 2048;
+    int blocks = pmh_grid(n_streams, 2048);
     hipLaunchKernelGGL(k_delta_scan, dim3(blocks), dim3(256), 0, stream,
                        streams, n_streams, sums, bases);
     return hipGetLastError();
@@ -5655,7 +5609,7 @@ hipError_t pmh_launch_delta_scan(const DeltaStream *streams,
 hipError_t pmh_launch_delta_emit(const DeltaChunk *chunks, int64_t n_chunks,
                                  const int64_t *bases, hipStream_t stream) {
     int64_t want = (n_chunks + 3) / 4;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     hipLaunchKernelGGL(k_delta_emit, dim3(blocks), dim3(256), 0, stream,
                        chunks, n_chunks, bases);
     return hipGetLastError();
@@ -5663,7 +5617,7 @@ hipError_t pmh_launch_delta_emit(const DeltaChunk *chunks, int64_t n_chunks,
 
 hipError_t pmh_launch_rle_decode(const RleChunk *chunks, int64_t n_chunks,
                                  int32_t *out, hipStream_t stream) {
-    int blocks = n_chunks < 4096 ? (int)(n_chunks ? n_chunks : 1) : 4096;
+    int blocks = pmh_grid(n_chunks);
     hipLaunchKernelGGL(k_rle_decode, dim3(blocks), dim3(256), 0, stream,
                        chunks, n_chunks, out);
     return hipGetLastError();
@@ -5674,7 +5628,7 @@ hipError_t pmh_launch_dict_gather(const int32_t *ids, const void *dict,
                                   hipStream_t stream) {
     int threads = 256;
     int64_t want = (n + threads - 1) / threads;
-    int blocks = want < 4096 ? (int)(want ? want : 1) : 4096;
+    int blocks = pmh_grid(want);
     if (esize == 4)
         hipLaunchKernelGGL(k_dict_gather_t<int32_t>, dim3(blocks),
                            dim3(threads), 0, stream, ids,
@@ -5687,7 +5641,5 @@ hipError_t pmh_launch_dict_gather(const int32_t *ids, const void *dict,
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
-
-}  // extern "C"
 
 }  // namespace pmh

@@ -604,60 +604,31 @@ struct Section {
     std::vector<Run> runs;
     int64_t total_rows = 0;
     int64_t n_tiles = 0;
-    // device-side descriptors
-    DevCol *key_cols = nullptr;   // [k]
-    DevCol *seq_cols = nullptr;   // [k]
-    DevCol *kind_cols = nullptr;  // [k]
-    DevCol *all_cols = nullptr;   // [k * n_cols] run-major
-    int64_t *lens_dev = nullptr;
-    int32_t *cuts = nullptr;
-    uint32_t *winners = nullptr;
-    int32_t *tile_counts = nullptr;
-    int64_t *tile_offsets = nullptr;
-    int64_t *total_dev = nullptr;
-    uint16_t *group_start = nullptr;  // partial-update member offsets
-    uint32_t *err_dev = nullptr;
-    // fused merge+emit path (dedup / first-row): per-tile lookback words +
-    // the tile ticket, zeroed per read
-    uint64_t *status = nullptr;
-    uint64_t *ticket = nullptr;
-    uint32_t *dense_winners = nullptr;  // split mode (PMH_FSPLIT)
-    // per-run tombstone byte arrays (deletion vectors; null entries = no
-    // DV) + the device pointer table the merge kernels consume
-    uint64_t *tombs_dev = nullptr;
+    // device-side state, as the launchers take it (kernels.h). runs_dev
+    // describes what the merge chain reads: the section's runs (plus a
+    // lookup plan's level slots), or the virtual runs of a hierarchical
+    // section
+    RunSet runs_dev;
+    TileSet tiles;
+    ChangelogSet cl;
+    // lookup changelog: k_lookup_probe writes one word per row of the
+    // level-0 runs
+    ProbeSet probe;
     bool any_tomb = false;
     // packed per-row validity (PU/agg emit): one u64 per row per run,
-    // bit c = column c non-null; built once per section by k_pack_valid
+    // bit c = column c non-null; rebuilt every read by k_pack_valid
+    // (runs_dev.masks is the device array of these)
     std::vector<uint64_t *> row_masks;
-    uint64_t **row_masks_dev = nullptr;  // [k] device array of the above
-    // full-compaction changelog chain
     // hierarchical sections (> PMH_MAX_RUNS runs): the reference spills
     // to disk (MergeSorter.spillMergeSort); here the winner fold is
     // ASSOCIATIVE for deduplicate/first-row (max/min by (seq, isAdd)), so
     // run batches merge on-device into VIRTUAL runs first (keeping delete
     // winners), then the normal chain merges the virtual runs.
     bool hier = false;
-    DevCol *rkeys = nullptr, *rseqs = nullptr, *rkinds = nullptr,
-           *rall = nullptr;          // descriptors over the REAL runs
-    int64_t *rlens = nullptr;
-    uint64_t *rtombs = nullptr;
+    RunSet real_dev;                 // the REAL runs (tombstones included)
     std::vector<int> blo, bhi;       // batch run ranges
     std::vector<int64_t> brows, bntiles;
-    std::vector<void **> bout_ptrs;      // [n_cols] device arrays per batch
-    std::vector<uint8_t **> bout_valid;
-    uint8_t *run_levels = nullptr;   // [k]
-    uint64_t *cl_entries = nullptr;  // 2 slots per group, provisional
-    uint64_t *cl_rows = nullptr;     // compacted rows (k_cl_finalize)
-    int32_t *cl_counts = nullptr;
-    int64_t *cl_offsets = nullptr;
-    int64_t *cl_total_dev = nullptr;
-    // lookup changelog: the descriptor tables carry n_lookup extra slots
-    // (the plan's lookup levels) after the k merge runs; k_lookup_probe
-    // writes one word per row of the level-0 runs
-    int n_lookup = 0;
-    int64_t *probe_off = nullptr;    // [k] word offset per run, -1 = no probe
-    uint32_t *probe_words = nullptr;
-    int64_t probe_max_rows = 0;      // longest probed run
+    std::vector<OutputSet> bout;     // per batch: its virtual run's columns
     std::vector<int64_t *> ckeys;  // per-run composite keys (k_composite)
     // batched decode work (all run-columns in ONE launch each)
     Rlev2Chunk *rlev2_all = nullptr;
@@ -680,6 +651,17 @@ struct Section {
     bool any_decode = false;  // dict or null-scatter work at read time
 };
 
+// One output stream of a plan (the main batch or the changelog batch):
+// device buffers reused per section, their host copies under
+// output = "host", and the pmh_col descriptors handed to the caller.
+struct OutBatch {
+    std::vector<void *> dev;       // per column
+    std::vector<uint8_t *> valid;  // per column; nullptr if never null
+    OutputSet set;                 // device arrays of the two above
+    std::vector<std::vector<uint8_t>> host, valid_host;
+    std::vector<pmh_col> cols;
+};
+
 }  // namespace pmh
 
 struct pmh_session_t {
@@ -689,10 +671,16 @@ struct pmh_session_t {
 struct pmh_plan_t {
     pmh_session_t *session = nullptr;
     hipStream_t stream = nullptr;
-    hipStream_t stream_b = nullptr;  // split-mode value emission overlap
     pmh::DeviceBufs bufs;
     std::vector<pmh::ColSpec> cols;  // key..., seq, kind, value...
-    int n_key_cols = 1;
+    // device tables over `cols` as the launchers take them (n_key_cols,
+    // the sequence.field columns and the aggregator codes included);
+    // hier_columns is the batch pass's view (int8/16 -> int32, so virtual
+    // runs hold the STORED width)
+    pmh::ColumnSet columns, hier_columns;
+    // engine bits of the merge flag word (PMH_FLAG_*), built once at the end
+    // of plan creation
+    int merge_flags = 0;
     bool drop_delete = true;
     bool ignore_delete = false;
     bool host_output = false;
@@ -702,14 +690,10 @@ struct pmh_plan_t {
                              // engines; PMH_FUSED=0 falls back for A/B)
     bool fsplit = false;     // split value emission (PMH_FSPLIT=1 A/B)
     bool agg = false;        // aggregation merge engine (uses PU member lists)
-    uint8_t *col_agg_dev = nullptr;  // per-column PMH_AGG_* codes
     // value filters (conjunction; applied to single-run sections only,
     // MergeFileSplitRead.java:227-239)
     std::vector<pmh::FilterTerm> filters;
     pmh::FilterTerm *filters_dev = nullptr;
-    uint8_t *hier_dtype_dev = nullptr;  // batch-pass dtype map (int8/16 ->
-                                        // int32 so virtual runs hold the
-                                        // STORED width)
     // composite key (>1 key column): order-preserving packed comparand
     bool composite_key = false;
     uint64_t key_shifts = 0, key_bits = 0;  // 8 bits per sub-key
@@ -722,11 +706,7 @@ struct pmh_plan_t {
     // act on their groups
     bool seqg = false;
     bool agg_retract = false;  // every aggregator retract-capable
-    // sequence.field (user-defined sequence comparator): compare listed
-    // value columns before the sequence number
-    int n_useq = 0;
-    int16_t *useq_dev = nullptr;
-    int n_seq_groups = 0;
+    pmh::SeqGroupSet seq_groups;
     // changelog-producer = full-compaction (FullChangelogMergeFunction-
     // Wrapper): a second output stream of changelog rows per read_next
     bool changelog = false;
@@ -742,34 +722,21 @@ struct pmh_plan_t {
     bool lookup = false;
     pmh::Section lookup_sec;
     int64_t cl_rows_last = 0;
-    std::vector<void *> out_dev2;
-    void **out_ptrs2_dev = nullptr;
-    std::vector<uint8_t *> out_valid2;
-    uint8_t **out_valid2_dev = nullptr;
-    std::vector<std::vector<uint8_t>> out_host2, out_valid_host2;
-    std::vector<pmh_col> batch_cols2;
-    uint8_t *col_group_dev = nullptr;
-    int16_t *sg_fields_dev = nullptr;
-    uint8_t *sg_nseq_dev = nullptr;
     std::vector<pmh::Section> sections;
     size_t cur_section = 0;
     int64_t rows_in_total = 0;
     int64_t encoded_bytes_total = 0;
-    // output buffers (reused per section)
-    std::vector<void *> out_dev;
-    void **out_ptrs_dev = nullptr;
-    uint8_t *col_dtype_dev = nullptr;
+    pmh::OutBatch out;   // main batch
+    pmh::OutBatch out2;  // changelog batch (changelog plans)
     std::vector<bool> col_nullable;        // any nulls staged for this col
-    uint8_t *col_nullable_dev = nullptr;
-    std::vector<uint8_t *> out_valid;      // per col; nullptr if never null
-    uint8_t **out_valid_dev = nullptr;     // device array of the above
-    std::vector<std::vector<uint8_t>> out_valid_host;
-    std::vector<std::vector<uint8_t>> out_host;
-    std::vector<pmh_col> batch_cols;
     std::vector<std::string> col_names;
     std::vector<std::unique_ptr<pmh::StrDict>> sdicts;  // per col; string only
     pmh_stats stats{};
     double h2d_ms = 0;
+    // the device buffers go with `bufs`, after the stream
+    ~pmh_plan_t() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace pmh {
@@ -2585,14 +2552,9 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec);
 static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
     const int n_real = (int)sec.runs.size();
     const int n_cols = (int)plan->cols.size();
-    // keep the real-run descriptors for the batch pass
-    sec.rkeys = sec.key_cols;
-    sec.rseqs = sec.seq_cols;
-    sec.rkinds = sec.kind_cols;
-    sec.rall = sec.all_cols;
-    sec.rlens = sec.lens_dev;
-    sec.rtombs = sec.tombs_dev;
-    sec.tombs_dev = nullptr;  // tombstones are consumed by the batch pass
+    // keep the real-run descriptors for the batch pass, which also consumes
+    // the tombstones
+    sec.real_dev = sec.runs_dev;
     // batches: <= PMH_MAX_RUNS runs and < 2^PMH_ROW_BITS input rows each
     {
         int lo = 0;
@@ -2624,24 +2586,24 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
     const int nb = (int)sec.blo.size();
     // batch-pass dtype map: int8/int16 emit as int32 so the virtual runs
     // hold the STORED width the second merge/emit pass reads
-    if (!plan->hier_dtype_dev) {
+    if (!plan->hier_columns.dtype) {
         std::vector<uint8_t> hd(n_cols);
         for (int c = 0; c < n_cols; c++) {
             uint8_t d = (uint8_t)plan->cols[c].dtype;
             hd[c] = (d == 1 || d == 2) ? 3 : d;
         }
-        plan->hier_dtype_dev = (uint8_t *)plan->bufs.alloc(n_cols);
-        if (!plan->hier_dtype_dev ||
-            hipMemcpy(plan->hier_dtype_dev, hd.data(), n_cols,
-                      hipMemcpyHostToDevice) != hipSuccess) {
+        uint8_t *hd_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+        if (!hd_dev || hipMemcpy(hd_dev, hd.data(), n_cols,
+                                 hipMemcpyHostToDevice) != hipSuccess) {
             set_error("H2D hier dtype map failed");
             return false;
         }
+        plan->hier_columns.dtype = hd_dev;
     }
     // virtual runs: one per batch; columns at stored width
     std::vector<DevCol> vkeys(nb), vseqs(nb), vkinds(nb), vall(nb * n_cols);
-    int seq_idx = plan->n_key_cols;
-    int kind_idx = plan->n_key_cols + 1;
+    const int seq_idx = plan->columns.seq_col();
+    const int kind_idx = plan->columns.kind_col();
     for (int b = 0; b < nb; b++) {
         std::vector<void *> outs(n_cols);
         std::vector<uint8_t *> valids(n_cols, nullptr);
@@ -2675,8 +2637,7 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
             set_error("H2D hier batch outputs failed");
             return false;
         }
-        sec.bout_ptrs.push_back(op);
-        sec.bout_valid.push_back(vp);
+        sec.bout.push_back(OutputSet{op, vp});
     }
     auto up = [&](const void *host, size_t n) -> void * {
         void *d = plan->bufs.alloc(n);
@@ -2685,13 +2646,18 @@ static bool build_hier_section(pmh_plan_t *plan, Section &sec) {
             return nullptr;
         return d;
     };
-    sec.key_cols = (DevCol *)up(vkeys.data(), nb * sizeof(DevCol));
-    sec.seq_cols = (DevCol *)up(vseqs.data(), nb * sizeof(DevCol));
-    sec.kind_cols = (DevCol *)up(vkinds.data(), nb * sizeof(DevCol));
-    sec.all_cols = (DevCol *)up(vall.data(), vall.size() * sizeof(DevCol));
-    sec.lens_dev = (int64_t *)plan->bufs.alloc(nb * 8);
-    if (!sec.key_cols || !sec.seq_cols || !sec.kind_cols || !sec.all_cols ||
-        !sec.lens_dev) {
+    // the chain's runs: the nb virtual runs, their lengths written by the
+    // batch pass
+    RunSet &vr = sec.runs_dev;
+    vr = RunSet{};
+    vr.k = vr.n_slots = nb;
+    vr.n_cols = n_cols;
+    vr.keys = (DevCol *)up(vkeys.data(), nb * sizeof(DevCol));
+    vr.seqs = (DevCol *)up(vseqs.data(), nb * sizeof(DevCol));
+    vr.kinds = (DevCol *)up(vkinds.data(), nb * sizeof(DevCol));
+    vr.cols = (DevCol *)up(vall.data(), vall.size() * sizeof(DevCol));
+    vr.lens = (int64_t *)plan->bufs.alloc(nb * 8);
+    if (!vr.keys || !vr.seqs || !vr.kinds || !vr.cols || !vr.lens) {
         set_error("hier descriptor allocation failed");
         return false;
     }
@@ -2709,11 +2675,10 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
     // part in partition or merge
     std::vector<Run> &lk_runs = plan->lookup_sec.runs;
     const int kt = k + (plan->lookup ? (int)lk_runs.size() : 0);
-    sec.n_lookup = kt - k;
     std::vector<DevCol> keyv(kt), seqv(kt), kindv(kt), allv(kt * n_cols);
     std::vector<int64_t> lens(kt);
-    int seq_idx = plan->n_key_cols;
-    int kind_idx = plan->n_key_cols + 1;
+    const int seq_idx = plan->columns.seq_col();
+    const int kind_idx = plan->columns.kind_col();
     if (plan->composite_key) sec.ckeys.assign(k, nullptr);
     for (int r = 0; r < kt; r++) {
         Run &run = r < k ? sec.runs[r] : lk_runs[r - k];
@@ -2744,64 +2709,72 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
         if (d && host) (void)hipMemcpy(d, host, n, hipMemcpyHostToDevice);
         return d;
     };
-    sec.key_cols = (DevCol *)up(keyv.data(), kt * sizeof(DevCol));
-    sec.seq_cols = (DevCol *)up(seqv.data(), kt * sizeof(DevCol));
-    sec.kind_cols = (DevCol *)up(kindv.data(), kt * sizeof(DevCol));
-    sec.all_cols = (DevCol *)up(allv.data(), allv.size() * sizeof(DevCol));
-    sec.lens_dev = (int64_t *)up(lens.data(), kt * sizeof(int64_t));
-    sec.cuts = (int32_t *)plan->bufs.alloc((sec.n_tiles + 1) * k * 4);
+    RunSet &rs = sec.runs_dev;
+    TileSet &ts = sec.tiles;
+    rs.k = k;
+    rs.n_slots = kt;
+    rs.n_cols = n_cols;
+    rs.keys = (DevCol *)up(keyv.data(), kt * sizeof(DevCol));
+    rs.seqs = (DevCol *)up(seqv.data(), kt * sizeof(DevCol));
+    rs.kinds = (DevCol *)up(kindv.data(), kt * sizeof(DevCol));
+    rs.cols = (DevCol *)up(allv.data(), allv.size() * sizeof(DevCol));
+    rs.lens = (int64_t *)up(lens.data(), kt * sizeof(int64_t));
+    ts.n_tiles = sec.n_tiles;
+    ts.cuts = (int32_t *)plan->bufs.alloc((sec.n_tiles + 1) * k * 4);
     if (plan->fused) {
         // single-pass path: no winners round-trip, no scan arrays — just
         // the per-tile lookback words and the tile ticket
-        sec.status = (uint64_t *)plan->bufs.alloc(sec.n_tiles * 8);
-        sec.ticket = (uint64_t *)plan->bufs.alloc(8);
-        if (!sec.status || !sec.ticket) return false;
+        ts.status = (uint64_t *)plan->bufs.alloc(sec.n_tiles * 8);
+        ts.ticket = (uint64_t *)plan->bufs.alloc(8);
+        if (!ts.status || !ts.ticket) return false;
         if (plan->fsplit) {
-            sec.dense_winners =
+            ts.dense_winners =
                 (uint32_t *)plan->bufs.alloc(sec.total_rows * 4);
-            if (!sec.dense_winners) return false;
+            if (!ts.dense_winners) return false;
         }
     } else {
-        sec.winners = (uint32_t *)plan->bufs.alloc(
+        ts.winners = (uint32_t *)plan->bufs.alloc(
             sec.n_tiles * (PMH_TILE_ROWS + PMH_MAX_RUNS) * 4);
-        sec.tile_counts = (int32_t *)plan->bufs.alloc(sec.n_tiles * 4);
-        sec.tile_offsets = (int64_t *)plan->bufs.alloc(sec.n_tiles * 8);
-        if (!sec.winners || !sec.tile_counts || !sec.tile_offsets)
-            return false;
+        ts.counts = (int32_t *)plan->bufs.alloc(sec.n_tiles * 4);
+        ts.offsets = (int64_t *)plan->bufs.alloc(sec.n_tiles * 8);
+        if (!ts.winners || !ts.counts || !ts.offsets) return false;
     }
     if (plan->changelog) {
         std::vector<uint8_t> lv(kt);
         for (int r = 0; r < kt; r++)
             lv[r] = (uint8_t)(r < k ? sec.runs[r] : lk_runs[r - k]).level;
-        sec.run_levels = (uint8_t *)up(lv.data(), kt);
+        rs.levels = (uint8_t *)up(lv.data(), kt);
+        ChangelogSet &cl = sec.cl;
         int64_t slots2 = sec.n_tiles * 2 * (PMH_TILE_ROWS + PMH_MAX_RUNS);
-        sec.cl_entries = (uint64_t *)plan->bufs.alloc(slots2 * 8);
-        sec.cl_rows = (uint64_t *)plan->bufs.alloc(slots2 * 8);
-        sec.cl_counts = (int32_t *)plan->bufs.alloc(sec.n_tiles * 4);
-        sec.cl_offsets = (int64_t *)plan->bufs.alloc(sec.n_tiles * 8);
-        sec.cl_total_dev = (int64_t *)plan->bufs.alloc(8);
-        if (!sec.run_levels || !sec.cl_entries || !sec.cl_rows ||
-            !sec.cl_counts || !sec.cl_offsets || !sec.cl_total_dev)
+        cl.entries = (uint64_t *)plan->bufs.alloc(slots2 * 8);
+        cl.rows = (uint64_t *)plan->bufs.alloc(slots2 * 8);
+        cl.counts = (int32_t *)plan->bufs.alloc(sec.n_tiles * 4);
+        cl.offsets = (int64_t *)plan->bufs.alloc(sec.n_tiles * 8);
+        cl.total = (int64_t *)plan->bufs.alloc(8);
+        cl.max_level = plan->max_level;
+        if (!rs.levels || !cl.entries || !cl.rows || !cl.counts ||
+            !cl.offsets || !cl.total)
             return false;
     }
     if (plan->lookup) {
         // probe words: one per row of the section's level-0 runs
+        ProbeSet &pr = sec.probe;
+        pr.n_levels = kt - k;
         std::vector<int64_t> po(k, -1);
         int64_t words = 0;
         for (int r = 0; r < k; r++) {
             if (sec.runs[r].level != 0) continue;
             po[r] = words;
             words += sec.runs[r].length;
-            sec.probe_max_rows =
-                std::max(sec.probe_max_rows, sec.runs[r].length);
+            pr.max_rows = std::max(pr.max_rows, sec.runs[r].length);
         }
-        sec.probe_off = (int64_t *)up(po.data(), k * sizeof(int64_t));
-        sec.probe_words = (uint32_t *)plan->bufs.alloc(words * 4);
-        if (!sec.probe_off || !sec.probe_words) return false;
+        pr.off = (int64_t *)up(po.data(), k * sizeof(int64_t));
+        pr.words = (uint32_t *)plan->bufs.alloc(words * 4);
+        if (!pr.off || !pr.words) return false;
     }
-    sec.total_dev = (int64_t *)plan->bufs.alloc(8);
-    sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
-    if (sec.err_dev) (void)hipMemset(sec.err_dev, 0, 4);
+    ts.total = (int64_t *)plan->bufs.alloc(8);
+    ts.err = (uint32_t *)plan->bufs.alloc(4);
+    if (ts.err) (void)hipMemset(ts.err, 0, 4);
     {
         std::vector<uint64_t> th(k, 0);
         for (int r = 0; r < k; r++) {
@@ -2809,14 +2782,14 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
             sec.any_tomb |= sec.runs[r].tomb != nullptr;
         }
         if (sec.any_tomb) {
-            sec.tombs_dev = (uint64_t *)up(th.data(), k * 8);
-            if (!sec.tombs_dev) return false;
+            rs.tombs = (uint64_t *)up(th.data(), k * 8);
+            if (!rs.tombs) return false;
         }
     }
     if (plan->pu) {
-        sec.group_start = (uint16_t *)plan->bufs.alloc(
+        ts.group_start = (uint16_t *)plan->bufs.alloc(
             sec.n_tiles * (PMH_TILE_ROWS + 1) * 2);
-        if (!sec.group_start) return false;
+        if (!ts.group_start) return false;
         bool any_valid = false;
         for (auto &run : sec.runs)
             for (auto &rc : run.cols)
@@ -2828,14 +2801,14 @@ static bool build_section_descriptors(pmh_plan_t *plan, Section &sec) {
                 sec.row_masks[r] = (uint64_t *)plan->bufs.alloc(n * 8);
                 if (!sec.row_masks[r]) return false;
             }
-            sec.row_masks_dev =
+            rs.masks =
                 (uint64_t **)up(sec.row_masks.data(), k * sizeof(void *));
-            if (!sec.row_masks_dev) return false;
+            if (!rs.masks) return false;
         }
     }
     if (!build_decode_tables(plan, sec)) return false;
-    return sec.key_cols && sec.seq_cols && sec.kind_cols && sec.all_cols &&
-           sec.lens_dev && sec.cuts && sec.total_dev && sec.err_dev;
+    return rs.keys && rs.seqs && rs.kinds && rs.cols && rs.lens && ts.cuts &&
+           ts.total && ts.err;
 }
 
 // Batched read-time decode work of a section's runs (one launch each
@@ -2897,12 +2870,12 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
     if (sec.n_ts) {
         // timestamp refusals land in the section's error word, like the
         // decimal ones below
-        if (!sec.err_dev) {
-            sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
-            if (!sec.err_dev || hipMemset(sec.err_dev, 0, 4) != hipSuccess)
+        if (!sec.tiles.err) {
+            sec.tiles.err = (uint32_t *)plan->bufs.alloc(4);
+            if (!sec.tiles.err || hipMemset(sec.tiles.err, 0, 4) != hipSuccess)
                 return false;
         }
-        for (auto &tu : all_t) tu.err_addr = (uint64_t)sec.err_dev;
+        for (auto &tu : all_t) tu.err_addr = (uint64_t)sec.tiles.err;
         sec.ts_all = (TsUnit *)up(all_t.data(), all_t.size() * sizeof(TsUnit));
         if (!sec.ts_all) return false;
     }
@@ -2910,12 +2883,12 @@ static bool build_decode_tables(pmh_plan_t *plan, Section &sec) {
     if (sec.n_varint) {
         // decimal range / scale violations land in the section's error word
         // (the lookup section owns none yet)
-        if (!sec.err_dev) {
-            sec.err_dev = (uint32_t *)plan->bufs.alloc(4);
-            if (!sec.err_dev || hipMemset(sec.err_dev, 0, 4) != hipSuccess)
+        if (!sec.tiles.err) {
+            sec.tiles.err = (uint32_t *)plan->bufs.alloc(4);
+            if (!sec.tiles.err || hipMemset(sec.tiles.err, 0, 4) != hipSuccess)
                 return false;
         }
-        for (auto &vu : all_u) vu.err_addr = (uint64_t)sec.err_dev;
+        for (auto &vu : all_u) vu.err_addr = (uint64_t)sec.tiles.err;
         sec.varint_all =
             (VarintUnit *)up(all_u.data(), all_u.size() * sizeof(VarintUnit));
         if (!sec.varint_all) return false;
@@ -3043,6 +3016,414 @@ static hipError_t launch_section_decode(pmh_plan_t *p, Section &sec,
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------ one read
+
+// Profiling fields of the merge flag word. Read per read: tests and the
+// profiling scripts vary them within a process.
+static int profile_flags() {
+    auto field = [](const char *name, int shift, int mask) {
+        const char *e = getenv(name);
+        return e ? (atoi(e) & mask) << shift : 0;
+    };
+    return field("PMH_ABLATE", PMH_FLAG_ABLATE_SHIFT, PMH_FLAG_ABLATE_MASK) |
+           field("PMH_FABL", PMH_FLAG_FABL_SHIFT, PMH_FLAG_FABL_MASK) |
+           field("PMH_FSTAGE", PMH_FLAG_FSTAGE_SHIFT, PMH_FLAG_FSTAGE_MASK);
+}
+
+// What a set device error word refuses the read with; empty for a clean one.
+static std::string error_word_message(const pmh_plan_t *p, uint32_t w) {
+    if (w & PMH_ERR_RETRACT) {
+        if (p->rrod)
+            return "remove-record-on-delete accepts INSERT/DELETE "
+                   "streams in v1; UPDATE_BEFORE records are not "
+                   "supported yet";
+        return std::string(p->agg ? "aggregation" : "partial-update") +
+               " with retract records is not supported "
+               "(the reference default also rejects them, "
+               "PartialUpdateMergeFunction.java:170-186); configure "
+               "'partial-update.remove-record-on-delete', or wait "
+               "for the sequence-group/retract-aggregator rounds";
+    }
+    if (w & PMH_ERR_FIRST_ROW_RETRACT)
+        return "first-row merge engine cannot accept DELETE/UPDATE_BEFORE "
+               "records; configure 'ignore-delete' to skip them "
+               "(FirstRowMergeFunction.java:49-59)";
+    if (w & PMH_ERR_LOOKBACK)
+        return "internal: fused merge lookback timed out waiting for a "
+               "predecessor tile";
+    if (w >> OTS_ERR_SHIFT) return orc_timestamp_error(w);
+    if (orc_decimal_bits(w)) return orc_decimal_error(w);
+    if (w & PMH_ERR_TOP_LEVEL_DUP)
+        return "Top level key-value already exists (two runs at "
+               "max_level hold the same key; "
+               "FullChangelogMergeFunctionWrapper.java:76-78 checkState)";
+    return "";
+}
+
+static bool hip_ok(const char *what, hipError_t e) {
+    if (e == hipSuccess) return true;
+    set_error("%s: %s", what, hipGetErrorString(e));
+    return false;
+}
+
+// Timing events of one read, destroyed on every way out of it. The stage
+// intervals are contiguous on the plan's stream:
+//   START decode DECODED partition PARTITIONED [lookup PROBED] merge MERGED
+//   scan SCANNED emit EMITTED
+struct StageEvents {
+    enum { START, DECODED, PARTITIONED, MERGED, SCANNED, EMITTED, N };
+    hipEvent_t ev[N] = {};
+    hipEvent_t probed = nullptr;  // lookup plans only
+    StageEvents() {
+        for (auto &e : ev) (void)hipEventCreate(&e);
+    }
+    ~StageEvents() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (probed) (void)hipEventDestroy(probed);
+    }
+    StageEvents(const StageEvents &) = delete;
+    StageEvents &operator=(const StageEvents &) = delete;
+    void record(int which, hipStream_t st) {
+        (void)hipEventRecord(ev[which], st);
+    }
+    void record_probed(hipStream_t st) {
+        (void)hipEventCreate(&probed);
+        (void)hipEventRecord(probed, st);
+    }
+    // after the stream synchronized
+    void add_to(pmh_stats &s) const {
+        auto ms = [](hipEvent_t a, hipEvent_t b) {
+            float v = 0;
+            (void)hipEventElapsedTime(&v, a, b);
+            return v;
+        };
+        s.decode_ms += ms(ev[START], ev[DECODED]);
+        s.partition_ms += ms(ev[DECODED], ev[PARTITIONED]);
+        if (probed) s.lookup_ms += ms(ev[PARTITIONED], probed);
+        s.merge_ms += ms(probed ? probed : ev[PARTITIONED], ev[MERGED]);
+        s.scan_ms += ms(ev[MERGED], ev[SCANNED]);
+        s.emit_ms += ms(ev[SCANNED], ev[EMITTED]);
+        s.total_device_ms += ms(ev[START], ev[EMITTED]);
+    }
+};
+
+// What one pmh_read_next carries from step to step.
+struct ReadPass {
+    pmh_plan_t *p;
+    Section &sec;
+    hipStream_t st;
+    int flags;      // plan flags + this read's profiling fields
+    RunSet runs;    // what the chain merges
+    TileSet tiles;  // ... in these tiles (a hierarchical batch pass leaves
+    int64_t rows;   // fewer rows, so fewer tiles, than the section staged)
+    StageEvents ev;
+};
+
+// Decode and the columns derived from it: batched RLEv2/byte-RLE +
+// PRESENT/def-level scatter (one launch each across every run-column — the
+// per-run-column launches serialized ~350 small kernels per step on C3),
+// parquet dictionary materialization per chunk, composite keys, packed
+// validity. The value filter runs after them, inside the partition interval.
+static bool read_decode(ReadPass &rp) {
+    pmh_plan_t *p = rp.p;
+    Section &sec = rp.sec;
+    const int k = (int)sec.runs.size();
+    const int n_cols = rp.runs.n_cols;
+    rp.ev.record(StageEvents::START, rp.st);
+    const char *dwhat = "decode";
+    // the call first: it names the launch that failed through dwhat
+    const hipError_t de = launch_section_decode(p, sec, rp.st, &dwhat);
+    if (!hip_ok(dwhat, de)) return false;
+    if (p->composite_key) {
+        // rebuilt per pass (decode-derived, like the validity masks)
+        for (int r = 0; r < k; r++) {
+            if (sec.runs[r].length <= 0) continue;
+            if (!hip_ok("composite",
+                        pmh_launch_composite(
+                            rp.runs.cols + (size_t)r * n_cols,
+                            p->columns.n_key_cols, p->key_shifts, p->key_bits,
+                            sec.runs[r].length, sec.ckeys[r], rp.st)))
+                return false;
+        }
+    }
+    if (rp.runs.masks) {
+        // rebuilt every pass: masks derive from the per-step level decode,
+        // so caching them across steps would skip timed work
+        for (int r = 0; r < k; r++) {
+            if (sec.runs[r].length <= 0) continue;
+            if (!hip_ok("pack_valid",
+                        pmh_launch_pack_valid(
+                            rp.runs.cols + (size_t)r * n_cols, n_cols,
+                            sec.runs[r].length, sec.row_masks[r], rp.st)))
+                return false;
+        }
+    }
+    rp.ev.record(StageEvents::DECODED, rp.st);
+    if (p->filters_dev && k == 1 && !sec.hier && sec.runs[0].tomb &&
+        sec.runs[0].length > 0) {
+        // value-filter pushdown: single-run sections only (overlapping
+        // sections would lose newer records — MergeFileSplitRead.java:
+        // 227-239); idempotent across repeats (OR into the tombstones)
+        if (!hip_ok("filter",
+                    pmh_launch_filter(rp.runs.cols, n_cols, p->filters_dev,
+                                      (int)p->filters.size(),
+                                      sec.runs[0].length, sec.runs[0].tomb,
+                                      rp.st)))
+            return false;
+    }
+    return true;
+}
+
+// Hierarchical batch pass: merge run batches into the virtual runs
+// (winner-of-winners — the dedup/first-row fold is associative; deletes are
+// KEPT here and drop only in the final chain). Leaves the chain the rows and
+// tiles of what the batches kept.
+static bool read_hier_batches(ReadPass &rp) {
+    pmh_plan_t *p = rp.p;
+    Section &sec = rp.sec;
+    const int nb = (int)sec.blo.size();
+    // no drop, no ignore
+    const int bflags = rp.flags & PMH_FLAG_FIRST_ROW;
+    for (int b = 0; b < nb; b++) {
+        const RunSet batch =
+            sec.real_dev.sub(sec.blo[b], sec.bhi[b] - sec.blo[b]);
+        // the batch's row count is its virtual run's length
+        const TileSet bt = sec.tiles.first(sec.bntiles[b], rp.runs.lens + b);
+        if (!hip_ok("hier partition",
+                    pmh_launch_partition(batch.keys, batch.lens, batch.k,
+                                         PMH_TILE_ROWS, bt.n_tiles + 1,
+                                         sec.brows[b], bt.cuts, rp.st)) ||
+            !hip_ok("hier merge",
+                    // never a changelog or lookup walk in the batch pass
+                    pmh_launch_merge_tiles(batch, bt, bflags, ChangelogSet{},
+                                           ProbeSet{}, rp.st)) ||
+            !hip_ok("hier scan",
+                    pmh_launch_scan_tiles(bt.counts, bt.n_tiles, bt.offsets,
+                                          bt.total, rp.st)) ||
+            !hip_ok("hier emit",
+                    pmh_launch_emit(batch, p->hier_columns, bt, sec.bout[b],
+                                    rp.st)))
+            return false;
+    }
+    std::vector<int64_t> vl(nb);
+    if (hipMemcpy(vl.data(), rp.runs.lens, nb * 8, hipMemcpyDeviceToHost) !=
+        hipSuccess)
+        return hip_ok("hier lens D2H", hipErrorUnknown);
+    rp.rows = 0;
+    for (int b = 0; b < nb; b++) rp.rows += vl[b];
+    rp.tiles.n_tiles = (rp.rows + PMH_TILE_ROWS - 1) / PMH_TILE_ROWS;
+    if (rp.tiles.n_tiles == 0) rp.tiles.n_tiles = 1;
+    return true;
+}
+
+static bool read_partition(ReadPass &rp) {
+    if (!hip_ok("partition",
+                pmh_launch_partition(rp.runs.keys, rp.runs.lens, rp.runs.k,
+                                     PMH_TILE_ROWS, rp.tiles.n_tiles + 1,
+                                     rp.rows, rp.tiles.cuts, rp.st)))
+        return false;
+    rp.ev.record(StageEvents::PARTITIONED, rp.st);
+    return true;
+}
+
+// Single-pass merge + emit: zero the lookback words + ticket, then one kernel
+// does merge, offsets and emission (scan/emit launches and the winners
+// round-trip disappear). Split mode (the default; PMH_FSPLIT=0 keeps in-kernel
+// emission): that kernel emits key/seq/kind and a dense winner list, and
+// k_emit_dense gathers the value columns after it. No scan: the scan interval
+// is empty.
+static bool read_fused(ReadPass &rp) {
+    pmh_plan_t *p = rp.p;
+    const TileSet &t = rp.tiles;
+    if (!hip_ok("status memset",
+                hipMemsetAsync(t.status, 0, t.n_tiles * 8, rp.st)) ||
+        !hip_ok("ticket memset", hipMemsetAsync(t.ticket, 0, 8, rp.st)) ||
+        !hip_ok("merge_emit",
+                pmh_launch_merge_emit(rp.runs, p->columns, t, rp.flags,
+                                      p->out.set, rp.st)))
+        return false;
+    rp.ev.record(StageEvents::MERGED, rp.st);
+    rp.ev.record(StageEvents::SCANNED, rp.st);
+    return !t.dense_winners ||
+           hip_ok("emit_dense", pmh_launch_emit_dense(rp.runs, p->columns, t,
+                                                      p->out.set, rp.st));
+}
+
+// The chain: lookup probe, tile merge, scan, the engine's emit.
+static bool read_chain(ReadPass &rp) {
+    pmh_plan_t *p = rp.p;
+    Section &sec = rp.sec;
+    const TileSet &t = rp.tiles;
+    if (p->cl_fold &&
+        ((rp.flags >> PMH_FLAG_ABLATE_SHIFT) & PMH_FLAG_ABLATE_MASK)) {
+        // an ablated merge leaves the changelog counts unwritten
+        set_error("PMH_ABLATE cannot be combined with a partial-update / "
+                  "aggregation changelog plan");
+        return false;
+    }
+    if (p->lookup) {
+        // point lookup into the upper levels for every level-0 row, before
+        // the merge walk consumes the probe words (timed as lookup_ms)
+        if (!hip_ok("lookup_probe",
+                    pmh_launch_lookup_probe(rp.runs, sec.probe, rp.st)))
+            return false;
+        rp.ev.record_probed(rp.st);
+    }
+    if (!hip_ok("merge_tiles",
+                pmh_launch_merge_tiles(rp.runs, t, rp.flags, sec.cl,
+                                       sec.probe, rp.st)))
+        return false;
+    rp.ev.record(StageEvents::MERGED, rp.st);
+    if (!hip_ok("scan_tiles",
+                pmh_launch_scan_tiles(t.counts, t.n_tiles, t.offsets, t.total,
+                                      rp.st)))
+        return false;
+    rp.ev.record(StageEvents::SCANNED, rp.st);
+    hipError_t e;
+    if (p->agg)
+        e = pmh_launch_emit_agg(rp.runs, p->columns, t, rp.flags, p->out.set,
+                                rp.st);
+    else if (p->pu && p->seqg)
+        e = pmh_launch_emit_pu_sg(rp.runs, p->columns, p->seq_groups, t,
+                                  rp.flags, p->out.set, rp.st);
+    else if (p->pu)
+        e = pmh_launch_emit_pu(rp.runs, p->columns, t, rp.flags, p->out.set,
+                               rp.st);
+    else
+        // a lookup winner may name a lookup-level slot past the k merge
+        // runs (runs.n_slots); a hierarchical chain reads its (contiguous)
+        // virtual runs
+        e = pmh_launch_emit(rp.runs, p->columns, t, p->out.set, rp.st);
+    return hip_ok("emit", e);
+}
+
+// Changelog rows of the section, inside the emit interval: compact the merge
+// pass's entries, scan the per-tile counts, gather into the changelog batch.
+// The folding engines' chain reads the merged rows from the main output.
+static bool read_changelog_tail(ReadPass &rp) {
+    pmh_plan_t *p = rp.p;
+    const ChangelogSet &cl = rp.sec.cl;
+    const TileSet &t = rp.tiles;
+    if (!p->changelog) return true;
+    const bool fold = p->cl_fold;
+    return hip_ok(fold ? "cl_finalize_out" : "cl_finalize",
+                  fold ? pmh_launch_cl_finalize_out(rp.runs, p->columns, t, cl,
+                                                    p->out.set, rp.st)
+                       : pmh_launch_cl_finalize(rp.runs, p->columns, t, cl,
+                                                rp.st)) &&
+           hip_ok("cl_scan",
+                  pmh_launch_scan_tiles(cl.counts, t.n_tiles, cl.offsets,
+                                        cl.total, rp.st)) &&
+           hip_ok(fold ? "cl_emit_out" : "cl_emit",
+                  fold ? pmh_launch_cl_emit_out(rp.runs, p->columns, t, cl,
+                                                p->out.set, p->out2.set,
+                                                rp.st)
+                       : pmh_launch_cl_emit(rp.runs, p->columns, t, cl,
+                                            p->out2.set, rp.st));
+}
+
+// The pmh_col descriptors of `rows` rows of one output stream, after their
+// D2H copies under output = "host".
+static bool assemble_batch(pmh_plan_t *p, OutBatch &ob, int64_t rows,
+                           const char *d2h_error,
+                           const char *d2h_valid_error) {
+    const int n_cols = (int)p->cols.size();
+    ob.cols.resize(n_cols);
+    if (p->host_output) {
+        ob.host.resize(n_cols);
+        ob.valid_host.resize(n_cols);
+        for (int c = 0; c < n_cols; c++) {
+            const size_t bytes = (size_t)rows * p->cols[c].out_esize;
+            ob.host[c].resize(bytes);
+            if (rows > 0 && hipMemcpy(ob.host[c].data(), ob.dev[c], bytes,
+                                      hipMemcpyDeviceToHost) != hipSuccess) {
+                set_error("%s", d2h_error);
+                return false;
+            }
+            if (!ob.valid[c]) continue;
+            ob.valid_host[c].resize(rows);
+            if (rows > 0 &&
+                hipMemcpy(ob.valid_host[c].data(), ob.valid[c], rows,
+                          hipMemcpyDeviceToHost) != hipSuccess) {
+                set_error("%s", d2h_valid_error);
+                return false;
+            }
+        }
+    }
+    for (int c = 0; c < n_cols; c++) {
+        pmh_col &pc = ob.cols[c];
+        pc.name = p->col_names[c].c_str();
+        pc.dtype = p->cols[c].is_bool ? PMH_DT_BOOL : p->cols[c].dtype;
+        pc.logical = p->cols[c].logical;
+        pc.data = p->host_output ? (const void *)ob.host[c].data()
+                                 : (const void *)ob.dev[c];
+        pc.valid = nullptr;
+        if (ob.valid[c])
+            pc.valid = p->host_output
+                           ? (const uint8_t *)ob.valid_host[c].data()
+                           : (const uint8_t *)ob.valid[c];
+        pc.dict_data = nullptr;
+        pc.dict_offsets = nullptr;
+        pc.dict_len = 0;
+        pc.precision = p->cols[c].precision;
+        pc.scale = p->cols[c].scale;
+        if (p->cols[c].dtype == PMH_DT_STRING && p->sdicts[c]) {
+            StrDict *sd = p->sdicts[c].get();
+            pc.dict_data = sd->bytes.data();
+            pc.dict_offsets = sd->offsets.data();
+            pc.dict_len = (int32_t)sd->offsets.size() - 1;
+        }
+    }
+    return true;
+}
+
+// Wait for the pass, refuse on a set error word, account the stage times and
+// hand out the batches. Returns the main batch's rows, -1 on error.
+static int64_t read_collect(ReadPass &rp, pmh_batch *out) {
+    pmh_plan_t *p = rp.p;
+    Section &sec = rp.sec;
+    int64_t total = 0;
+    int64_t cl_total = 0;
+    uint32_t err_word = 0;
+    if (!hip_ok("total D2H",
+                hipMemcpyAsync(&total, rp.tiles.total, 8,
+                               hipMemcpyDeviceToHost, rp.st)) ||
+        (p->changelog && sec.cl.total &&
+         !hip_ok("cl total D2H",
+                 hipMemcpyAsync(&cl_total, sec.cl.total, 8,
+                                hipMemcpyDeviceToHost, rp.st))) ||
+        !hip_ok("err D2H", hipMemcpyAsync(&err_word, rp.tiles.err, 4,
+                                          hipMemcpyDeviceToHost, rp.st)) ||
+        !hip_ok("stream sync", hipStreamSynchronize(rp.st)))
+        return -1;
+    const std::string refusal = error_word_message(p, err_word);
+    if (!refusal.empty()) {
+        set_error("%s", refusal.c_str());
+        return -1;
+    }
+    rp.ev.add_to(p->stats);
+    p->stats.rows_in += sec.total_rows;
+    p->stats.rows_out += total;
+
+    if (!assemble_batch(p, p->out, total, "D2H output failed",
+                        "D2H validity failed"))
+        return -1;
+    if (p->changelog) {
+        p->cl_rows_last = cl_total;
+        if (!assemble_batch(p, p->out2, cl_total, "D2H changelog failed",
+                            "D2H changelog validity failed"))
+            return -1;
+    }
+    if (out) {
+        out->n_rows = total;
+        out->n_cols = (int32_t)p->cols.size();
+        out->device = p->host_output ? -1 : p->session->device;
+        out->cols = p->out.cols.data();
+    }
+    return total;
+}
+
 }  // namespace pmh
 
 // ==================================================================== C ABI
@@ -3158,8 +3539,8 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 plan->key_bits |= (uint64_t)(uint8_t)bits << (8 * i);
             }
         }
-        plan->n_key_cols = (int)kc.arr.size();
-        plan->composite_key = plan->n_key_cols > 1;
+        plan->columns.n_key_cols = (int)kc.arr.size();
+        plan->composite_key = plan->columns.n_key_cols > 1;
         for (const auto &c : kc.arr)
             if (!add_col(c)) return nullptr;
         {  // _SEQUENCE_NUMBER, _VALUE_KIND (SpecialFields.java:79-83)
@@ -3170,6 +3551,7 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
         }
         for (const auto &c : j["value_cols"].arr)
             if (!add_col(c)) return nullptr;
+        plan->columns.n_cols = (int)plan->cols.size();
         plan->sdicts.resize(plan->cols.size());  // before staging touches it
         std::string engine = j["merge_engine"].as_str("deduplicate");
         if (engine == "partial-update") {
@@ -3185,7 +3567,7 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                     set_error("at most 16 sequence groups in v1");
                     return nullptr;
                 }
-                const int first_val = plan->n_key_cols + 2;
+                const int first_val = plan->columns.first_val();
                 const int n_cols = (int)plan->cols.size();
                 std::vector<uint8_t> cg(n_cols, 0xff);
                 std::vector<int16_t> sf(sgs.arr.size() * 4, -1);
@@ -3235,22 +3617,21 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                         cg[c] = (uint8_t)g;
                     }
                 }
-                plan->n_seq_groups = (int)sgs.arr.size();
-                plan->col_group_dev = (uint8_t *)plan->bufs.alloc(n_cols);
-                plan->sg_fields_dev =
-                    (int16_t *)plan->bufs.alloc(sf.size() * 2);
-                plan->sg_nseq_dev = (uint8_t *)plan->bufs.alloc(ns.size());
-                if (!plan->col_group_dev || !plan->sg_fields_dev ||
-                    !plan->sg_nseq_dev ||
-                    hipMemcpy(plan->col_group_dev, cg.data(), n_cols,
+                uint8_t *cg_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+                int16_t *sf_dev = (int16_t *)plan->bufs.alloc(sf.size() * 2);
+                uint8_t *ns_dev = (uint8_t *)plan->bufs.alloc(ns.size());
+                if (!cg_dev || !sf_dev || !ns_dev ||
+                    hipMemcpy(cg_dev, cg.data(), n_cols,
                               hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(plan->sg_fields_dev, sf.data(), sf.size() * 2,
+                    hipMemcpy(sf_dev, sf.data(), sf.size() * 2,
                               hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(plan->sg_nseq_dev, ns.data(), ns.size(),
+                    hipMemcpy(ns_dev, ns.data(), ns.size(),
                               hipMemcpyHostToDevice) != hipSuccess) {
                     set_error("H2D of sequence-group tables failed");
                     return nullptr;
                 }
+                plan->seq_groups =
+                    SeqGroupSet{cg_dev, sf_dev, ns_dev, (int)sgs.arr.size()};
             }
         } else if (engine == "first-row") {
             plan->first_row = true;  // FirstRowMergeFunction.java:32-77
@@ -3290,7 +3671,7 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                     set_error("at most 4 sequence fields in v1");
                     return nullptr;
                 }
-                const int first_val = plan->n_key_cols + 2;
+                const int first_val = plan->columns.first_val();
                 const int n_cols = (int)plan->cols.size();
                 std::vector<int16_t> uc;
                 for (const auto &fj : uf.arr) {
@@ -3306,15 +3687,17 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                     }
                     uc.push_back((int16_t)idx);
                 }
-                plan->n_useq = (int)uc.size();
-                plan->useq_dev =
-                    (int16_t *)plan->bufs.alloc(uc.size() * 2);
-                if (!plan->useq_dev ||
-                    hipMemcpy(plan->useq_dev, uc.data(), uc.size() * 2,
+                // sequence.field (user-defined sequence comparator): the
+                // listed value columns compare before the sequence number
+                int16_t *uc_dev = (int16_t *)plan->bufs.alloc(uc.size() * 2);
+                if (!uc_dev ||
+                    hipMemcpy(uc_dev, uc.data(), uc.size() * 2,
                               hipMemcpyHostToDevice) != hipSuccess) {
                     set_error("H2D of sequence fields failed");
                     return nullptr;
                 }
+                plan->columns.useq = uc_dev;
+                plan->columns.n_useq = (int)uc.size();
             }
         }
         plan->drop_delete = j["drop_delete"].as_bool(true);
@@ -3383,10 +3766,10 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             // stays as the path for user-defined sequence fields (its
             // comparator lives there) and behind PMH_FUSED=1 for A/B.
             const char *pf = getenv("PMH_FUSED");
-            bool want_fused = pf ? pf[0] != '0' : (plan->n_useq > 0);
+            bool want_fused = pf ? pf[0] != '0' : (plan->columns.n_useq > 0);
             plan->fused = !plan->pu && want_fused;
             if (plan->changelog && plan->fused) {
-                if (plan->n_useq > 0 || (pf && pf[0] != '0')) {
+                if (plan->columns.n_useq > 0 || (pf && pf[0] != '0')) {
                     set_error("changelog_producer=%s runs on "
                               "the classic merge chain (no sequence.field / "
                               "PMH_FUSED=1 combination in v1)",
@@ -3395,7 +3778,7 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 }
                 plan->fused = false;
             }
-            if (plan->n_useq > 0 && !plan->pu && !plan->fused) {
+            if (plan->columns.n_useq > 0 && !plan->pu && !plan->fused) {
                 set_error("sequence.field needs the fused merge path "
                           "(unset PMH_FUSED=0)");
                 return nullptr;
@@ -3507,11 +3890,6 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             set_error("hipStreamCreate failed");
             return nullptr;
         }
-        if (plan->fsplit &&
-            hipStreamCreate(&plan->stream_b) != hipSuccess) {
-            set_error("hipStreamCreate (b) failed");
-            return nullptr;
-        }
 
         auto sections = interval_partition(files, plan->changelog);
         auto t0 = std::chrono::steady_clock::now();
@@ -3602,19 +3980,14 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             }
             if (ls.n_varint || ls.n_ts) {
                 uint32_t ew = 0;
-                if (hipMemcpy(&ew, ls.err_dev, 4, hipMemcpyDeviceToHost) !=
+                if (hipMemcpy(&ew, ls.tiles.err, 4, hipMemcpyDeviceToHost) !=
                     hipSuccess) {
                     set_error("lookup levels: err D2H failed");
                     return nullptr;
                 }
-                if (ew >> OTS_ERR_SHIFT) {
-                    set_error("lookup levels: %s",
-                              orc_timestamp_error(ew).c_str());
-                    return nullptr;
-                }
-                if (orc_decimal_bits(ew)) {
-                    set_error("lookup levels: %s",
-                              orc_decimal_error(ew).c_str());
+                const std::string msg = error_word_message(plan.get(), ew);
+                if (!msg.empty()) {
+                    set_error("lookup levels: %s", msg.c_str());
                     return nullptr;
                 }
             }
@@ -3699,13 +4072,13 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
             }
             dts[c] = (uint8_t)plan->cols[c].dtype;
         }
-        plan->out_dev = outs;
-        plan->out_ptrs_dev = (void **)plan->bufs.alloc(n_cols * sizeof(void *));
-        plan->col_dtype_dev = (uint8_t *)plan->bufs.alloc(n_cols);
-        if (hipMemcpy(plan->out_ptrs_dev, outs.data(),
-                      n_cols * sizeof(void *),
+        plan->out.dev = outs;
+        void **out_ptrs_dev =
+            (void **)plan->bufs.alloc(n_cols * sizeof(void *));
+        uint8_t *col_dtype_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+        if (hipMemcpy(out_ptrs_dev, outs.data(), n_cols * sizeof(void *),
                       hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(plan->col_dtype_dev, dts.data(), n_cols,
+            hipMemcpy(col_dtype_dev, dts.data(), n_cols,
                       hipMemcpyHostToDevice) != hipSuccess) {
             set_error("H2D of output descriptors failed");
             return nullptr;
@@ -3720,64 +4093,66 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
         for (auto &run : plan->lookup_sec.runs)
             for (int c = 0; c < n_cols; c++)
                 if (run.cols[c].has_nulls) plan->col_nullable[c] = true;
-        plan->out_valid.assign(n_cols, nullptr);
+        plan->out.valid.assign(n_cols, nullptr);
         std::vector<uint8_t> nul(n_cols, 0);
         for (int c = 0; c < n_cols; c++) {
             nul[c] = plan->col_nullable[c] ? 1 : 0;
             if (plan->col_nullable[c]) {
-                plan->out_valid[c] = (uint8_t *)plan->bufs.alloc(max_rows);
-                if (!plan->out_valid[c]) {
+                // validity outputs keep emit off the streamed kernel
+                plan->columns.any_nullable = 1;
+                plan->out.valid[c] = (uint8_t *)plan->bufs.alloc(max_rows);
+                if (!plan->out.valid[c]) {
                     set_error("validity allocation failed");
                     return nullptr;
                 }
             }
         }
-        plan->col_nullable_dev = (uint8_t *)plan->bufs.alloc(n_cols);
-        plan->out_valid_dev =
+        uint8_t *col_nullable_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+        uint8_t **out_valid_dev =
             (uint8_t **)plan->bufs.alloc(n_cols * sizeof(void *));
-        if (hipMemcpy(plan->col_nullable_dev, nul.data(), n_cols,
+        if (hipMemcpy(col_nullable_dev, nul.data(), n_cols,
                       hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(plan->out_valid_dev, plan->out_valid.data(),
+            hipMemcpy(out_valid_dev, plan->out.valid.data(),
                       n_cols * sizeof(void *),
                       hipMemcpyHostToDevice) != hipSuccess) {
             set_error("H2D of validity descriptors failed");
             return nullptr;
         }
+        plan->out.set = OutputSet{out_ptrs_dev, out_valid_dev};
+        plan->columns.dtype = col_dtype_dev;
+        plan->columns.nullable = col_nullable_dev;
         if (plan->changelog) {
             // changelog outputs: up to 2 rows per key group <= 2 * inputs
             int64_t cap2 = 2 * max_rows;
-            plan->out_dev2.resize(n_cols);
-            plan->out_valid2.assign(n_cols, nullptr);
+            OutBatch &o2 = plan->out2;
+            o2.dev.resize(n_cols);
+            o2.valid.assign(n_cols, nullptr);
             for (int c = 0; c < n_cols; c++) {
-                plan->out_dev2[c] =
-                    plan->bufs.alloc(cap2 * plan->cols[c].out_esize);
-                if (!plan->out_dev2[c]) {
+                o2.dev[c] = plan->bufs.alloc(cap2 * plan->cols[c].out_esize);
+                if (!o2.dev[c]) {
                     set_error("changelog output allocation failed");
                     return nullptr;
                 }
                 if (plan->col_nullable[c]) {
-                    plan->out_valid2[c] =
-                        (uint8_t *)plan->bufs.alloc(cap2);
-                    if (!plan->out_valid2[c]) {
+                    o2.valid[c] = (uint8_t *)plan->bufs.alloc(cap2);
+                    if (!o2.valid[c]) {
                         set_error("changelog validity allocation failed");
                         return nullptr;
                     }
                 }
             }
-            plan->out_ptrs2_dev =
-                (void **)plan->bufs.alloc(n_cols * sizeof(void *));
-            plan->out_valid2_dev =
+            void **ptrs2 = (void **)plan->bufs.alloc(n_cols * sizeof(void *));
+            uint8_t **valid2 =
                 (uint8_t **)plan->bufs.alloc(n_cols * sizeof(void *));
-            if (!plan->out_ptrs2_dev || !plan->out_valid2_dev ||
-                hipMemcpy(plan->out_ptrs2_dev, plan->out_dev2.data(),
-                          n_cols * sizeof(void *),
+            if (!ptrs2 || !valid2 ||
+                hipMemcpy(ptrs2, o2.dev.data(), n_cols * sizeof(void *),
                           hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(plan->out_valid2_dev, plan->out_valid2.data(),
-                          n_cols * sizeof(void *),
+                hipMemcpy(valid2, o2.valid.data(), n_cols * sizeof(void *),
                           hipMemcpyHostToDevice) != hipSuccess) {
                 set_error("H2D of changelog descriptors failed");
                 return nullptr;
             }
+            o2.set = OutputSet{ptrs2, valid2};
         }
         for (auto &cs : plan->cols) plan->col_names.push_back(cs.name);
         if (plan->agg) {
@@ -3799,7 +4174,7 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 if (s == "primary_key") return PMH_AGG_PRIMARY_KEY;
                 return -1;
             };
-            const int first_val = plan->n_key_cols + 2;
+            const int first_val = plan->columns.first_val();
             for (const auto &kv : j["aggregations"].obj) {
                 int idx = -1;
                 for (int c = first_val; c < n_cols; c++)
@@ -3878,14 +4253,32 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 }
                 plan->agg_retract = all_rt && !plan->rrod;
             }
-            plan->col_agg_dev = (uint8_t *)plan->bufs.alloc(n_cols);
-            if (!plan->col_agg_dev ||
-                hipMemcpy(plan->col_agg_dev, ca.data(), n_cols,
-                          hipMemcpyHostToDevice) != hipSuccess) {
+            uint8_t *ca_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+            if (!ca_dev || hipMemcpy(ca_dev, ca.data(), n_cols,
+                                     hipMemcpyHostToDevice) != hipSuccess) {
                 set_error("H2D of aggregator codes failed");
                 return nullptr;
             }
+            plan->columns.agg = ca_dev;
         }
+        // the batch pass of hierarchical sections reads the same columns at
+        // their stored width (build_hier_section made its dtype map)
+        {
+            const uint8_t *hd = plan->hier_columns.dtype;
+            plan->hier_columns = plan->columns;
+            plan->hier_columns.dtype = hd;
+        }
+        plan->merge_flags =
+            (plan->drop_delete ? PMH_FLAG_DROP_DELETE : 0) |
+            (plan->ignore_delete ? PMH_FLAG_IGNORE_DELETE : 0) |
+            (plan->pu ? PMH_FLAG_MEMBERS : 0) |
+            (plan->first_row ? PMH_FLAG_FIRST_ROW : 0) |
+            (plan->rrod ? PMH_FLAG_RROD : 0) |
+            (plan->seqg ? PMH_FLAG_SEQ_GROUPS : 0) |
+            (plan->agg_retract ? PMH_FLAG_AGG_RETRACT : 0) |
+            (plan->cl_row_dedup ? PMH_FLAG_CL_ROW_DEDUP : 0) |
+            (plan->lookup ? PMH_FLAG_LOOKUP : 0) |
+            (plan->cl_fold ? PMH_FLAG_FOLD_CL : 0);
     } catch (const std::exception &e) {
         set_error("plan parse: %s", e.what());
         return nullptr;
@@ -3902,490 +4295,19 @@ int64_t pmh_read_next(pmh_plan_t *p, pmh_batch *out) {
     if (p->cur_section >= p->sections.size()) return 0;
     (void)hipSetDevice(p->session->device);
     Section &sec = p->sections[p->cur_section++];
-    hipStream_t st = p->stream;
-    int k = (int)sec.runs.size();
-    int n_cols = (int)p->cols.size();
-
-    hipEvent_t ev[6];
-    for (auto &e : ev) (void)hipEventCreate(&e);
-    // ev: 0 start, 1 decode done, 2 partition done, 3 merge done,
-    //     4 scan done, 5 emit done
-
-    hipEvent_t ev_lk = nullptr;  // lookup probe done (lookup changelog)
-    auto fail = [&](const char *what, hipError_t e) -> int64_t {
-        set_error("%s: %s", what, hipGetErrorString(e));
-        for (auto &evv : ev) (void)hipEventDestroy(evv);
-        if (ev_lk) (void)hipEventDestroy(ev_lk);
-        return -1;
-    };
-
-    (void)hipEventRecord(ev[0], st);
-    // decode: batched RLEv2/byte-RLE + PRESENT/def-level scatter (one
-    // launch each across every run-column — the per-run-column launches
-    // serialized ~350 small kernels per step on C3), plus parquet
-    // dictionary materialization per chunk
-    {
-        const char *dwhat = "decode";
-        hipError_t de = launch_section_decode(p, sec, st, &dwhat);
-        if (de != hipSuccess) return fail(dwhat, de);
-    }
-    if (p->composite_key) {
-        // rebuilt per pass (decode-derived, like the validity masks)
-        for (int r = 0; r < k; r++) {
-            if (sec.runs[r].length <= 0) continue;
-            hipError_t ce = pmh_launch_composite(
-                sec.all_cols + (size_t)r * n_cols, p->n_key_cols,
-                p->key_shifts, p->key_bits, sec.runs[r].length, sec.ckeys[r],
-                st);
-            if (ce != hipSuccess) return fail("composite", ce);
-        }
-    }
-    if (sec.row_masks_dev) {
-        // rebuilt every pass: masks derive from the per-step level decode,
-        // so caching them across steps would skip timed work
-        for (int r = 0; r < k; r++) {
-            if (sec.runs[r].length <= 0) continue;
-            hipError_t pe = pmh_launch_pack_valid(
-                sec.all_cols + (size_t)r * n_cols, n_cols,
-                sec.runs[r].length, sec.row_masks[r], st);
-            if (pe != hipSuccess) return fail("pack_valid", pe);
-        }
-    }
-    (void)hipEventRecord(ev[1], st);
-    if (p->filters_dev && k == 1 && !sec.hier && sec.runs[0].tomb &&
-        sec.runs[0].length > 0) {
-        // value-filter pushdown: single-run sections only (overlapping
-        // sections would lose newer records — MergeFileSplitRead.java:
-        // 227-239); idempotent across repeats (OR into the tombstones)
-        hipError_t fe = pmh_launch_filter(
-            sec.all_cols, n_cols, p->filters_dev, (int)p->filters.size(),
-            sec.runs[0].length, sec.runs[0].tomb, st);
-        if (fe != hipSuccess) return fail("filter", fe);
-    }
-    int64_t n_tiles_eff = sec.n_tiles;
-    int64_t rows_eff = sec.total_rows;
-    int any_nullable = 0;  // validity outputs keep emit off the streamed kernel
-    for (bool nb : p->col_nullable) any_nullable |= nb ? 1 : 0;
-    if (sec.hier) {
-        // batch pass: merge run batches into the virtual runs
-        // (winner-of-winners — the dedup/first-row fold is associative;
-        // deletes are KEPT here and drop only in the final chain)
-        const int nb = (int)sec.blo.size();
-        k = nb;
-        const int bflags = p->first_row ? 8 : 0;  // no drop, no ignore
-        for (int b = 0; b < nb; b++) {
-            int lo = sec.blo[b];
-            int kb = sec.bhi[b] - lo;
-            int64_t btiles = sec.bntiles[b];
-            hipError_t hb = pmh_launch_partition(
-                sec.rkeys + lo, sec.rlens + lo, kb, PMH_TILE_ROWS,
-                btiles + 1, sec.brows[b], sec.cuts, st);
-            if (hb != hipSuccess) return fail("hier partition", hb);
-            hb = pmh_launch_merge_tiles(
-                sec.rkeys + lo, sec.rseqs + lo, sec.rkinds + lo,
-                sec.rlens + lo, kb, sec.cuts, btiles, PMH_TILE_ROWS, bflags,
-                sec.rtombs ? sec.rtombs + lo : nullptr, sec.winners,
-                sec.tile_counts, sec.group_start, sec.err_dev, nullptr, 0,
-                nullptr, nullptr, nullptr, nullptr, st);
-            if (hb != hipSuccess) return fail("hier merge", hb);
-            hb = pmh_launch_scan_tiles(sec.tile_counts, btiles,
-                                       sec.tile_offsets, sec.lens_dev + b,
-                                       st);
-            if (hb != hipSuccess) return fail("hier scan", hb);
-            hb = pmh_launch_emit(sec.rall + (size_t)lo * n_cols,
-                                 p->hier_dtype_dev, p->col_nullable_dev,
-                                 any_nullable, n_cols, kb, kb, sec.cuts,
-                                 sec.rlens + lo,
-                                 sec.winners, sec.tile_counts,
-                                 sec.tile_offsets, btiles, PMH_TILE_ROWS,
-                                 sec.lens_dev + b, sec.bout_ptrs[b],
-                                 sec.bout_valid[b], st);
-            if (hb != hipSuccess) return fail("hier emit", hb);
-        }
-        std::vector<int64_t> vl(nb);
-        if (hipMemcpy(vl.data(), sec.lens_dev, nb * 8,
-                      hipMemcpyDeviceToHost) != hipSuccess)
-            return fail("hier lens D2H", hipErrorUnknown);
-        rows_eff = 0;
-        for (int b = 0; b < nb; b++) rows_eff += vl[b];
-        n_tiles_eff = (rows_eff + PMH_TILE_ROWS - 1) / PMH_TILE_ROWS;
-        if (n_tiles_eff == 0) n_tiles_eff = 1;
-    }
-    hipError_t e = pmh_launch_partition(sec.key_cols, sec.lens_dev, k,
-                                        PMH_TILE_ROWS, n_tiles_eff + 1,
-                                        rows_eff, sec.cuts, st);
-    if (e != hipSuccess) return fail("partition", e);
-    (void)hipEventRecord(ev[2], st);
-    int flags = (p->drop_delete ? 1 : 0) | (p->ignore_delete ? 2 : 0) |
-                (p->pu ? 4 : 0) | (p->first_row ? 8 : 0) |
-                (p->rrod ? 16 : 0) | (p->seqg ? 32 : 0) |
-                (p->agg_retract ? 64 : 0);
-    if (const char *ab = getenv("PMH_ABLATE"))  // profiling-only phase knob
-        flags |= (atoi(ab) & 0xf) << 8;
-    if (const char *ab = getenv("PMH_FABL"))  // fused-kernel phase knob
-        flags |= (atoi(ab) & 0x3) << 12;      // (profiling only)
-    if (const char *fs = getenv("PMH_FSTAGE"))  // A/B: LDS-staged emission
-        flags |= (atoi(fs) & 1) << 14;          // instead of direct gather
+    ReadPass rp{p,         sec,          p->stream,
+                p->merge_flags | profile_flags(),
+                sec.runs_dev,  sec.tiles, sec.total_rows, {}};
+    if (!read_decode(rp)) return -1;
+    if (sec.hier && !read_hier_batches(rp)) return -1;
+    if (!read_partition(rp)) return -1;
     if (p->fused) {
-        // single-pass merge + emit: zero the lookback words + ticket, then
-        // one kernel does merge, offsets and emission (scan/emit launches
-        // and the winners round-trip disappear)
-        e = hipMemsetAsync(sec.status, 0, n_tiles_eff * 8, st);
-        if (e != hipSuccess) return fail("status memset", e);
-        e = hipMemsetAsync(sec.ticket, 0, 8, st);
-        if (e != hipSuccess) return fail("ticket memset", e);
-        int key_col = p->composite_key ? -1 : 0;
-        {
-            // split mode: chunk the tile space and pipeline — kernel A
-            // (merge + key/seq/kind + dense winners) for chunk i+1 runs on
-            // the plan stream while kernel B (value gather) for chunk i
-            // runs on stream_b, gated by a per-chunk event. Non-split: one
-            // A launch does everything.
-            // measured: A/B stream overlap is a wash — B's full-occupancy
-            // gathers stretch A by about what the B tail saves (ch=1
-            // 7.19 ms vs ch=8 7.57 on the same box) — so the default is
-            // ONE chunk (A then B); PMH_FCHUNKS re-enables the pipeline
-            int64_t want = 1;
-            if (const char *fc = getenv("PMH_FCHUNKS"))
-                want = sec.dense_winners ? atoll(fc) : 1;
-            const int64_t n_chunks =
-                want < 1 ? 1 : (want > 8 ? 8 : want);
-            const int64_t per =
-                (n_tiles_eff + n_chunks - 1) / n_chunks;
-            hipEvent_t cev[8];
-            for (int64_t c = 0; c < n_chunks; c++)
-                (void)hipEventCreateWithFlags(&cev[c],
-                                              hipEventDisableTiming);
-            for (int64_t c = 0; c < n_chunks; c++) {
-                int64_t t0 = c * per;
-                int64_t t1 = t0 + per < n_tiles_eff ? t0 + per : n_tiles_eff;
-                if (t0 >= t1) { (void)hipEventRecord(cev[c], st); continue; }
-                if (c > 0) {  // ticket restarts per chunk
-                    e = hipMemsetAsync(sec.ticket, 0, 8, st);
-                    if (e != hipSuccess) return fail("ticket memset", e);
-                }
-                e = pmh_launch_merge_emit(
-                    sec.key_cols, sec.seq_cols, sec.kind_cols, sec.lens_dev,
-                    k, sec.cuts, t0, t1, n_tiles_eff, PMH_TILE_ROWS, flags,
-                    sec.tombs_dev,
-                    sec.all_cols, p->col_dtype_dev, p->col_nullable_dev,
-                    n_cols, key_col, p->n_key_cols, p->n_key_cols + 1,
-                    p->useq_dev, p->n_useq,
-                    sec.status, sec.ticket, sec.total_dev, sec.dense_winners,
-                    p->out_ptrs_dev, p->out_valid_dev, sec.err_dev, st);
-                if (e != hipSuccess) return fail("merge_emit", e);
-                (void)hipEventRecord(cev[c], st);
-            }
-            (void)hipEventRecord(ev[3], st);
-            (void)hipEventRecord(ev[4], st);
-            if (sec.dense_winners) {
-                hipStream_t sb = p->stream_b;
-                for (int64_t c = 0; c < n_chunks; c++) {
-                    int64_t t0 = c * per;
-                    int64_t t1 =
-                        t0 + per < n_tiles_eff ? t0 + per : n_tiles_eff;
-                    if (t0 >= t1) continue;
-                    (void)hipStreamWaitEvent(sb, cev[c], 0);
-                    e = pmh_launch_emit_dense(
-                        sec.all_cols, p->col_dtype_dev, p->col_nullable_dev,
-                        n_cols, key_col, p->n_key_cols, p->n_key_cols + 1,
-                        sec.dense_winners, t0, t1, sec.status,
-                        p->out_ptrs_dev, p->out_valid_dev, sb);
-                    if (e != hipSuccess) return fail("emit_dense", e);
-                }
-                // rejoin: the plan stream waits for the last B chunk
-                hipEvent_t done;
-                (void)hipEventCreateWithFlags(&done, hipEventDisableTiming);
-                (void)hipEventRecord(done, sb);
-                (void)hipStreamWaitEvent(st, done, 0);
-                (void)hipEventDestroy(done);
-            }
-            (void)hipEventRecord(ev[5], st);
-            for (int64_t c = 0; c < n_chunks; c++)
-                (void)hipEventDestroy(cev[c]);
-        }
-        goto collect;
-    }
-    if (p->cl_fold && ((flags >> 8) & 0xf)) {
-        // an ablated merge leaves the changelog counts unwritten
-        set_error("PMH_ABLATE cannot be combined with a partial-update / "
-                  "aggregation changelog plan");
-        for (auto &evv : ev) (void)hipEventDestroy(evv);
+        if (!read_fused(rp)) return -1;
+    } else if (!read_chain(rp) || !read_changelog_tail(rp)) {
         return -1;
     }
-    if (p->lookup) {
-        // point lookup into the upper levels for every level-0 row, before
-        // the merge walk consumes the probe words (timed as lookup_ms)
-        (void)hipEventCreate(&ev_lk);
-        e = pmh_launch_lookup_probe(sec.key_cols, sec.lens_dev, sec.probe_off,
-                                    k, sec.n_lookup, sec.probe_max_rows,
-                                    sec.probe_words, st);
-        if (e != hipSuccess) return fail("lookup_probe", e);
-        (void)hipEventRecord(ev_lk, st);
-    }
-    e = pmh_launch_merge_tiles(sec.key_cols, sec.seq_cols, sec.kind_cols,
-                               sec.lens_dev, k, sec.cuts, n_tiles_eff,
-                               PMH_TILE_ROWS,
-                               flags | (p->cl_row_dedup ? 128 : 0) |
-                                   (p->lookup ? PMH_FLAG_LOOKUP : 0) |
-                                   (p->cl_fold ? PMH_FLAG_FOLD_CL : 0),
-                               sec.tombs_dev, sec.winners,
-                               sec.tile_counts, sec.group_start, sec.err_dev,
-                               sec.run_levels, p->max_level, sec.cl_entries,
-                               sec.cl_counts, sec.probe_words, sec.probe_off,
-                               st);
-    if (e != hipSuccess) return fail("merge_tiles", e);
-    (void)hipEventRecord(ev[3], st);
-    e = pmh_launch_scan_tiles(sec.tile_counts, n_tiles_eff, sec.tile_offsets,
-                              sec.total_dev, st);
-    if (e != hipSuccess) return fail("scan_tiles", e);
-    (void)hipEventRecord(ev[4], st);
-    if (p->agg) {
-        e = pmh_launch_emit_agg(
-            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev,
-            p->col_agg_dev, n_cols, k, p->n_key_cols, p->n_key_cols + 1,
-            flags, sec.winners, sec.group_start, sec.tile_offsets,
-            n_tiles_eff, PMH_TILE_ROWS, sec.total_dev, sec.row_masks_dev,
-            p->out_ptrs_dev, p->out_valid_dev, st);
-    } else if (p->pu && p->seqg) {
-        e = pmh_launch_emit_pu_sg(
-            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols, k,
-            p->n_key_cols, p->n_key_cols + 1, flags, p->col_group_dev,
-            p->sg_fields_dev, p->sg_nseq_dev, p->n_seq_groups, sec.winners,
-            sec.group_start, sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS,
-            sec.total_dev, sec.row_masks_dev, p->out_ptrs_dev,
-            p->out_valid_dev, st);
-    } else if (p->pu) {
-        e = pmh_launch_emit_pu(
-            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols, k,
-            p->n_key_cols, p->n_key_cols + 1, flags, sec.winners,
-            sec.group_start, sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS,
-            sec.total_dev, sec.row_masks_dev, p->out_ptrs_dev,
-            p->out_valid_dev, st);
-    } else {
-        // a lookup winner may name a lookup-level slot past the k merge
-        // runs; a hierarchical chain reads its (contiguous) virtual runs
-        e = pmh_launch_emit(sec.all_cols, p->col_dtype_dev,
-                            p->col_nullable_dev, any_nullable, n_cols, k,
-                            sec.hier ? k : k + sec.n_lookup, sec.cuts,
-                            sec.lens_dev, sec.winners,
-                            sec.tile_counts, sec.tile_offsets, n_tiles_eff,
-                            PMH_TILE_ROWS, sec.total_dev, p->out_ptrs_dev,
-                            p->out_valid_dev, st);
-    }
-    if (e != hipSuccess) return fail("emit", e);
-    if (p->cl_fold) {
-        // folded chain: the merged rows are in the main output by now
-        e = pmh_launch_cl_finalize_out(
-            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols,
-            p->n_key_cols + 2, k, sec.cl_entries, sec.cl_rows, sec.cl_counts,
-            sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS, p->out_ptrs_dev,
-            p->out_valid_dev, st);
-        if (e != hipSuccess) return fail("cl_finalize_out", e);
-        e = pmh_launch_scan_tiles(sec.cl_counts, n_tiles_eff, sec.cl_offsets,
-                                  sec.cl_total_dev, st);
-        if (e != hipSuccess) return fail("cl_scan", e);
-        e = pmh_launch_cl_emit_out(
-            sec.all_cols, p->col_dtype_dev, p->col_nullable_dev, n_cols, k,
-            p->n_key_cols + 1, sec.cl_rows, sec.cl_counts, sec.cl_offsets,
-            sec.tile_offsets, n_tiles_eff, PMH_TILE_ROWS, p->out_ptrs_dev,
-            p->out_valid_dev, p->out_ptrs2_dev, p->out_valid2_dev, st);
-        if (e != hipSuccess) return fail("cl_emit_out", e);
-    } else if (p->changelog) {
-        e = pmh_launch_cl_finalize(sec.all_cols, p->col_dtype_dev, n_cols,
-                                   p->n_key_cols + 2, k, sec.cl_entries,
-                                   sec.cl_rows, sec.cl_counts, n_tiles_eff,
-                                   PMH_TILE_ROWS, st);
-        if (e != hipSuccess) return fail("cl_finalize", e);
-        e = pmh_launch_scan_tiles(sec.cl_counts, n_tiles_eff, sec.cl_offsets,
-                                  sec.cl_total_dev, st);
-        if (e != hipSuccess) return fail("cl_scan", e);
-        e = pmh_launch_cl_emit(sec.all_cols, p->col_dtype_dev,
-                               p->col_nullable_dev, n_cols,
-                               p->n_key_cols + 1, sec.cl_rows, sec.cl_counts,
-                               sec.cl_offsets, n_tiles_eff, PMH_TILE_ROWS,
-                               p->out_ptrs2_dev, p->out_valid2_dev, st);
-        if (e != hipSuccess) return fail("cl_emit", e);
-    }
-    (void)hipEventRecord(ev[5], st);
-
-collect:
-    int64_t total = 0;
-    int64_t cl_total = 0;
-    uint32_t err_word = 0;
-    e = hipMemcpyAsync(&total, sec.total_dev, 8, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return fail("total D2H", e);
-    if (p->changelog && sec.cl_total_dev) {
-        e = hipMemcpyAsync(&cl_total, sec.cl_total_dev, 8,
-                           hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) return fail("cl total D2H", e);
-    }
-    e = hipMemcpyAsync(&err_word, sec.err_dev, 4, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return fail("err D2H", e);
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail("stream sync", e);
-    if (err_word & 1) {
-        if (p->rrod)
-            set_error("remove-record-on-delete accepts INSERT/DELETE "
-                      "streams in v1; UPDATE_BEFORE records are not "
-                      "supported yet");
-        else
-            set_error("%s with retract records is not supported "
-                      "(the reference default also rejects them, "
-                      "PartialUpdateMergeFunction.java:170-186); configure "
-                      "'partial-update.remove-record-on-delete', or wait "
-                      "for the sequence-group/retract-aggregator rounds",
-                      p->agg ? "aggregation" : "partial-update");
-        return -1;
-    }
-    if (err_word & 2) {
-        set_error("first-row merge engine cannot accept DELETE/UPDATE_BEFORE "
-                  "records; configure 'ignore-delete' to skip them "
-                  "(FirstRowMergeFunction.java:49-59)");
-        return -1;
-    }
-    if (err_word & 4) {
-        set_error("internal: fused merge lookback timed out waiting for a "
-                  "predecessor tile");
-        return -1;
-    }
-    if (err_word >> OTS_ERR_SHIFT) {
-        set_error("%s", orc_timestamp_error(err_word).c_str());
-        return -1;
-    }
-    if (orc_decimal_bits(err_word)) {
-        set_error("%s", orc_decimal_error(err_word).c_str());
-        return -1;
-    }
-    if (err_word & 8) {
-        set_error("Top level key-value already exists (two runs at "
-                  "max_level hold the same key; "
-                  "FullChangelogMergeFunctionWrapper.java:76-78 checkState)");
-        return -1;
-    }
-
-    float ms;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    p->stats.decode_ms += ms;
-    (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
-    p->stats.partition_ms += ms;
-    if (ev_lk) {
-        (void)hipEventElapsedTime(&ms, ev[2], ev_lk);
-        p->stats.lookup_ms += ms;
-    }
-    (void)hipEventElapsedTime(&ms, ev_lk ? ev_lk : ev[2], ev[3]);
-    p->stats.merge_ms += ms;
-    (void)hipEventElapsedTime(&ms, ev[3], ev[4]);
-    p->stats.scan_ms += ms;
-    (void)hipEventElapsedTime(&ms, ev[4], ev[5]);
-    p->stats.emit_ms += ms;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[5]);
-    p->stats.total_device_ms += ms;
-    for (auto &evv : ev) (void)hipEventDestroy(evv);
-    if (ev_lk) (void)hipEventDestroy(ev_lk);
-
-    p->stats.rows_in += sec.total_rows;
-    p->stats.rows_out += total;
-
-    // assemble batch
-    p->batch_cols.resize(n_cols);
-    if (p->host_output) {
-        p->out_host.resize(n_cols);
-        for (int c = 0; c < n_cols; c++) {
-            p->out_host[c].resize(total * p->cols[c].out_esize);
-            if (total > 0 &&
-                hipMemcpy(p->out_host[c].data(), p->out_dev[c],
-                          total * p->cols[c].out_esize,
-                          hipMemcpyDeviceToHost) != hipSuccess) {
-                set_error("D2H output failed");
-                return -1;
-            }
-        }
-    }
-    if (p->host_output) {
-        p->out_valid_host.resize(n_cols);
-        for (int c = 0; c < n_cols; c++) {
-            if (!p->out_valid[c]) continue;
-            p->out_valid_host[c].resize(total);
-            if (total > 0 &&
-                hipMemcpy(p->out_valid_host[c].data(), p->out_valid[c], total,
-                          hipMemcpyDeviceToHost) != hipSuccess) {
-                set_error("D2H validity failed");
-                return -1;
-            }
-        }
-    }
-    for (int c = 0; c < n_cols; c++) {
-        pmh_col &pc = p->batch_cols[c];
-        pc.name = p->col_names[c].c_str();
-        pc.dtype = p->cols[c].is_bool ? PMH_DT_BOOL : p->cols[c].dtype;
-        pc.logical = p->cols[c].logical;
-        pc.data = p->host_output ? (const void *)p->out_host[c].data()
-                                 : (const void *)p->out_dev[c];
-        pc.valid = nullptr;
-        if (p->out_valid[c])
-            pc.valid = p->host_output
-                           ? (const uint8_t *)p->out_valid_host[c].data()
-                           : (const uint8_t *)p->out_valid[c];
-        pc.dict_data = nullptr;
-        pc.dict_offsets = nullptr;
-        pc.dict_len = 0;
-        pc.precision = p->cols[c].precision;
-        pc.scale = p->cols[c].scale;
-        if (p->cols[c].dtype == PMH_DT_STRING && p->sdicts[c]) {
-            StrDict *sd = p->sdicts[c].get();
-            pc.dict_data = sd->bytes.data();
-            pc.dict_offsets = sd->offsets.data();
-            pc.dict_len = (int32_t)sd->offsets.size() - 1;
-        }
-    }
-    if (p->changelog) {
-        p->cl_rows_last = cl_total;
-        p->batch_cols2.resize(n_cols);
-        if (p->host_output) {
-            p->out_host2.resize(n_cols);
-            p->out_valid_host2.resize(n_cols);
-            for (int c = 0; c < n_cols; c++) {
-                p->out_host2[c].resize(cl_total * p->cols[c].out_esize);
-                if (cl_total > 0 &&
-                    hipMemcpy(p->out_host2[c].data(), p->out_dev2[c],
-                              cl_total * p->cols[c].out_esize,
-                              hipMemcpyDeviceToHost) != hipSuccess) {
-                    set_error("D2H changelog failed");
-                    return -1;
-                }
-                if (p->out_valid2[c]) {
-                    p->out_valid_host2[c].resize(cl_total);
-                    if (cl_total > 0 &&
-                        hipMemcpy(p->out_valid_host2[c].data(),
-                                  p->out_valid2[c], cl_total,
-                                  hipMemcpyDeviceToHost) != hipSuccess) {
-                        set_error("D2H changelog validity failed");
-                        return -1;
-                    }
-                }
-            }
-        }
-        for (int c = 0; c < n_cols; c++) {
-            pmh_col pc = p->batch_cols[c];  // share names/dict/decimal info
-            pc.data = p->host_output ? (const void *)p->out_host2[c].data()
-                                     : (const void *)p->out_dev2[c];
-            pc.valid = nullptr;
-            if (p->out_valid2[c])
-                pc.valid =
-                    p->host_output
-                        ? (const uint8_t *)p->out_valid_host2[c].data()
-                        : (const uint8_t *)p->out_valid2[c];
-            p->batch_cols2[c] = pc;
-        }
-    }
-    if (out) {
-        out->n_rows = total;
-        out->n_cols = n_cols;
-        out->device = p->host_output ? -1 : p->session->device;
-        out->cols = p->batch_cols.data();
-    }
-    return total;
+    rp.ev.record(StageEvents::EMITTED, rp.st);
+    return read_collect(rp, out);
 }
 
 // Changelog batch of the LAST pmh_read_next call (changelog_producer =
@@ -4400,7 +4322,7 @@ int64_t pmh_changelog_next(pmh_plan_t *p, pmh_batch *out) {
         out->n_rows = p->cl_rows_last;
         out->n_cols = (int32_t)p->cols.size();
         out->device = p->host_output ? -1 : p->session->device;
-        out->cols = p->batch_cols2.data();
+        out->cols = p->out2.cols.data();
     }
     return p->cl_rows_last;
 }
@@ -4413,9 +4335,7 @@ int pmh_plan_reset(pmh_plan_t *p) {
 
 int pmh_plan_close(pmh_plan_t *p) {
     if (!p) return 0;
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    if (p->stream_b) (void)hipStreamDestroy(p->stream_b);
-    delete p;
+    delete p;  // its destructor releases the stream and the buffers
     return 0;
 }
 
