@@ -443,6 +443,39 @@ int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
  * Lets a test tell a streamed read from a fallback. */
 int pmh_debug_last_emit_kernel(void);
 
+/* Which partial-update emit kernel the last read of this process launched: 0
+ * none yet, 1 k_emit_pu (no sequence groups), 2 k_emit_pu_sg (sequence
+ * groups, no aggregate functions), 3 k_emit_pu_sga (aggregate functions on
+ * group fields). */
+int pmh_debug_last_pu_emit_kernel(void);
+
+/* One key group through the partial-update fold with aggregate functions
+ * inside sequence groups, on the host, through the same core k_emit_pu_sga
+ * runs on the device (pu_agg_core.h; PartialUpdateMergeFunction.java
+ * :149-397 and the FieldAggregators). The group has n_members (1..32)
+ * records in ascending (sequence number, isAdd) order: kinds[x] is member
+ * x's RowKind byte; values[x * n_cols + c] its field c as 64 bits (integers
+ * sign-extended, FLOAT32 the raw 32 bits sign-extended, FLOAT64 the raw
+ * bits) and valid[x * n_cols + c] != 0 when it is non-null. dtypes[c] is a
+ * pmh_dtype code. Sequence groups as in the plan: col_group[c] = group id or
+ * 0xff, sg_fields[g * 4 + j] = group g's sequence-field columns, sg_nseq[g]
+ * of them (1..4). col_agg[c] = 0 last_non_null_value, 1 last_value, 2
+ * first_value, 3 first_non_null_value, 4 sum, 5 max, 6 min, | 0x80 for
+ * ignore-retract, or 0xff for no aggregate function. Writes the merged row
+ * to out_values / out_valid ([n_cols]), the result RowKind to *out_kind (a
+ * single member passes through with its own), the index of the member whose
+ * sequence number the result carries to *out_last (-1: none, the number is
+ * 0) and to *out_unsupported whether a retract met an aggregate function
+ * without retraction. Returns 0, or -1 with pmh_last_error() set. */
+int pmh_debug_pu_agg_fold(int n_members, const int8_t *kinds, int n_cols,
+                          const uint8_t *dtypes, const int64_t *values,
+                          const uint8_t *valid, int n_groups,
+                          const uint8_t *col_group, const int16_t *sg_fields,
+                          const uint8_t *sg_nseq, const uint8_t *col_agg,
+                          int ignore_delete, int64_t *out_values,
+                          uint8_t *out_valid, int32_t *out_kind,
+                          int32_t *out_last, int32_t *out_unsupported);
+
 /* Parse one JSON number the way the plan descriptor's numbers are parsed
  * (minKey/maxKey, rowCount, integer filter literals): a token without '.',
  * 'e' or 'E' is an exact int64, a fractional token rounds to nearest, an

@@ -85,12 +85,14 @@ constexpr int PMH_FLAG_FOLD_CL = 1 << 16;
 
 // ----------------------------------------------------------- device error word
 // One uint32 per section (TileSet::err), OR-ed by the kernels and read back
-// after every pass. Bits 0-3 are the merge kernels'; the ORC decode bits sit
+// after every pass. Bits 0-4 are the merge and emit kernels'; the ORC decode bits sit
 // above them (ODC_ERR_*, orc_decimal_core.h; OTS_ERR_*, orc_timestamp_core.h).
 constexpr uint32_t PMH_ERR_RETRACT = 1u << 0;       // engine rejects retracts
 constexpr uint32_t PMH_ERR_FIRST_ROW_RETRACT = 1u << 1;
 constexpr uint32_t PMH_ERR_LOOKBACK = 1u << 2;      // fused lookback timed out
 constexpr uint32_t PMH_ERR_TOP_LEVEL_DUP = 1u << 3; // two max_level records
+// partial-update: a retract reached an aggregate function without retract()
+constexpr uint32_t PMH_ERR_PU_AGG_RETRACT = 1u << 4;
 
 // ------------------------------------------------------- launcher arguments
 // Plain views of device memory the plan owns. A Section and the plan hold
@@ -148,12 +150,18 @@ struct ColumnSet {
 };
 
 // partial-update sequence groups: col_group[c] = group id or 0xff; fields
-// packs 4 sequence-field column indices per group
+// packs 4 sequence-field column indices per group. With aggregate functions
+// on group fields (col_agg != nullptr): grp_cols[grp_off[g] .. grp_off[g + 1])
+// lists group g's fields that are no sequence fields, and col_agg[c] is the
+// column's PMH_AGG_* code (| PMH_AGG_IGNORE_RETRACT) or 0xff for none.
 struct SeqGroupSet {
     const uint8_t *col_group = nullptr;
     const int16_t *fields = nullptr;
     const uint8_t *nseq = nullptr;
     int n_groups = 0;
+    const int16_t *grp_cols = nullptr;
+    const uint16_t *grp_off = nullptr;
+    const uint8_t *col_agg = nullptr;
 };
 
 // A section's tile state. Every tile holds PMH_TILE_ROWS merged rows.
@@ -431,7 +439,9 @@ enum {
 constexpr uint8_t PMH_AGG_IGNORE_RETRACT = 0x80;
 // PartialUpdate with sequence groups (PartialUpdateMergeFunction.java:
 // 219-377): per-group last-prefix-max-achiever resolution; retracts null
-// their group members (SeqGroupSet); no per-field aggregators in v1.
+// their group members (SeqGroupSet). groups.col_agg set: some group field
+// carries an aggregate function, and k_emit_pu_sga folds every member
+// (pu_agg_core.h); its refused retractions land in tiles.err.
 hipError_t pmh_launch_emit_pu_sg(const RunSet &runs, const ColumnSet &columns,
                                  const SeqGroupSet &groups,
                                  const TileSet &tiles, int flags,
@@ -440,6 +450,16 @@ hipError_t pmh_launch_emit_pu_sg(const RunSet &runs, const ColumnSet &columns,
 hipError_t pmh_launch_emit_agg(const RunSet &runs, const ColumnSet &columns,
                                const TileSet &tiles, int flags,
                                const OutputSet &out, hipStream_t stream);
+
+// Which partial-update emit kernel the last pmh_launch_emit_pu /
+// pmh_launch_emit_pu_sg call chose (tests pin the selection)
+enum {
+    PMH_PU_EMIT_NONE = 0,
+    PMH_PU_EMIT_OVERLAY = 1,  // k_emit_pu
+    PMH_PU_EMIT_SG = 2,       // k_emit_pu_sg
+    PMH_PU_EMIT_SGA = 3,      // k_emit_pu_sga
+};
+int pmh_last_pu_emit_kernel();
 
 hipError_t pmh_launch_dict_gather(const int32_t *ids, const void *dict,
                                   int64_t n, void *out, int esize,

@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "lookup_core.h"
 #include "partition_core.h"
+#include "pu_agg_core.h"
 #include "zstd_core.h"
 
 #define DEV __device__ __forceinline__
@@ -3026,8 +3027,9 @@ __global__ void k_emit_pu(const DevCol *cols, const uint8_t *col_dtype,
 // PartialUpdateMergeFunction.java:219-282; retractWithSequenceGroup
 // :301-377; isEmptySequenceGroup :284-299; initRow :399-407; getResult
 // :389-397). Streams may carry INSERT/UPDATE_AFTER/UPDATE_BEFORE/DELETE;
-// retracts act only on their sequence groups (no per-field aggregators in
-// v1 — their retract support is a later round).
+// retracts act only on their sequence groups. Plans whose group fields carry
+// aggregate functions run k_emit_pu_sga below instead; this kernel serves
+// the plans without them.
 //
 // The reference's sequential per-key fold reduces, per group, to the LAST
 // PREFIX-MAX ACHIEVER over the members' sequence-field tuples (non-empty
@@ -3197,6 +3199,139 @@ __global__ void k_emit_pu_sg(const DevCol *cols, const uint8_t *col_dtype,
             if (out_valid[c]) out_valid[c][i] = ok;
         }
     }
+}
+
+// --------------------------------------------------------- k_emit_pu_sga
+//
+// PartialUpdate with sequence groups AND aggregate functions on group fields
+// (fields.<f>.aggregate-function / ignore-retract / default-aggregate-
+// function). An aggregated field takes a contribution from EVERY member of
+// its group, agg or aggReversed by how the member's tuple compared with the
+// row's running tuple at that moment, so the last-prefix-max shortcut of
+// k_emit_pu_sg does not apply. The fold itself is pu_agg_core.h, shared with
+// the host entry pmh_debug_pu_agg_fold.
+//
+// One thread per output row. The sequence groups loop OUTERMOST and no
+// per-thread table is indexed by group (a run-time-indexed local array puts
+// the whole array in scratch, see k_emit_agg): per group, one walk over the
+// members leaves two 32-bit masks and the tuple holder in registers
+// (pac_scan_group), then that group's columns fold and store
+// (grp_cols[grp_off[g] .. grp_off[g + 1]): its fields that are no sequence
+// fields). Member kinds load once per row into a 64-bit word (2 bits x <= 32
+// members). Plain columns go last. Member fields load inside the fold, in
+// member order; no register cache of the first members.
+// col_agg[c]: PMH_AGG_* | PMH_AGG_IGNORE_RETRACT, or PAC_NONE. A retract that
+// reaches an aggregator without retract() sets PMH_ERR_PU_AGG_RETRACT.
+struct PuMembers {
+    const DevCol *cols;
+    const uint8_t *col_dtype;
+    uint64_t *const *run_masks;
+    const uint32_t *mem;  // the key group's member words
+    int n_cols;
+    DEV bool valid(int x, int c) const {
+        const uint32_t m = mem[x];
+        if (run_masks) return ((member_mask(run_masks, m) >> c) & 1) != 0;
+        return member_valid(cols, n_cols, m, c) != 0;
+    }
+    DEV int64_t load(int x, int c) const {
+        return member_load(cols, n_cols, mem[x], c, col_dtype[c]);
+    }
+};
+
+// output row i of the plan's columns; the kernel writes the sequence-number
+// and kind columns itself
+struct PuRowSink {
+    void *const *out_ptrs;
+    uint8_t *const *out_valid;
+    const uint8_t *col_dtype;
+    int64_t i;
+    int seq_col, kind_col;
+    DEV bool own(int c) const { return c == seq_col || c == kind_col; }
+    DEV void put(int c, int64_t bits, bool ok) {
+        out_store(out_ptrs[c], col_dtype[c], i, bits);
+        if (out_valid[c]) out_valid[c][i] = ok;
+    }
+};
+
+static_assert(PAC_LAST_NON_NULL == PMH_AGG_LAST_NON_NULL &&
+                  PAC_LAST_VALUE == PMH_AGG_LAST_VALUE &&
+                  PAC_FIRST_VALUE == PMH_AGG_FIRST_VALUE &&
+                  PAC_FIRST_NON_NULL == PMH_AGG_FIRST_NON_NULL &&
+                  PAC_SUM == PMH_AGG_SUM && PAC_MAX == PMH_AGG_MAX &&
+                  PAC_MIN == PMH_AGG_MIN &&
+                  PAC_IGNORE_RETRACT == PMH_AGG_IGNORE_RETRACT,
+              "pu_agg_core.h aggregator codes follow PMH_AGG_*");
+static_assert(PAC_DT_INT8 == PMH_DT_INT8 && PAC_DT_INT16 == PMH_DT_INT16 &&
+                  PAC_DT_INT32 == PMH_DT_INT32 &&
+                  PAC_DT_INT64 == PMH_DT_INT64 &&
+                  PAC_DT_FLOAT32 == PMH_DT_FLOAT32 &&
+                  PAC_DT_FLOAT64 == PMH_DT_FLOAT64,
+              "pu_agg_core.h dtype codes follow PMH_DT_*");
+static_assert(PAC_MAX_MEMBERS == PMH_MAX_RUNS,
+              "a key group has at most one member per run");
+
+__global__ void k_emit_pu_sga(const DevCol *cols, const uint8_t *col_dtype,
+                              const uint8_t *col_nullable, int n_cols, int k,
+                              int seq_col, int kind_col, int flags,
+                              const uint8_t *col_group,
+                              const int16_t *sg_fields,
+                              const uint8_t *sg_nseq, int n_groups,
+                              const int16_t *grp_cols,
+                              const uint16_t *grp_off,
+                              const uint8_t *col_agg,
+                              const uint32_t *members,
+                              const uint16_t *group_start,
+                              const int64_t *tile_offsets, int64_t n_tiles,
+                              int64_t tile_rows, const int64_t *total_out,
+                              uint64_t *const *run_masks,
+                              void *const *out_ptrs,
+                              uint8_t *const *out_valid, uint32_t *err_flag) {
+    const bool ignore_delete = flags & PMH_FLAG_IGNORE_DELETE;
+    const int64_t total = *total_out;
+    const int64_t slice_lo = slice_lo_of(total);
+    const int64_t slice_hi = slice_hi_of(total);
+    const PacTables tables{n_cols,   n_groups, col_dtype, col_group, sg_fields,
+                           sg_nseq,  grp_cols, grp_off,   col_agg};
+    int64_t t = -1;
+    bool bad = false;
+    for (int64_t i = slice_lo + threadIdx.x; i < slice_hi; i += blockDim.x) {
+        if (t < 0) t = tile_seek(tile_offsets, n_tiles, i);
+        t = tile_walk(tile_offsets, n_tiles, t, i);
+        const int64_t g = i - tile_offsets[t];
+        const uint16_t *gs = &group_start[t * (tile_rows + 1)];
+        const uint32_t *mem = &members[t * (tile_rows + PMH_MAX_RUNS)];
+        const int32_t ms = gs[g], me = gs[g + 1];
+        // a key group holds at most one member per run
+        const int gn = me - ms < PMH_MAX_RUNS ? me - ms : PMH_MAX_RUNS;
+        const PuMembers a{cols, col_dtype, run_masks, mem + ms, n_cols};
+        PuRowSink sink{out_ptrs, out_valid, col_dtype, i, seq_col, kind_col};
+        uint64_t kinds = 0;
+        for (int x = 0; x < gn; x++) {
+            const int32_t kd = col_load<int32_t>(
+                member_col(cols, n_cols, mem[ms + x], kind_col),
+                member_row(mem[ms + x]));
+            kinds |= (uint64_t)(kd & 3) << (2 * x);
+        }
+        if (gn == 1) {
+            // ReducerMergeFunctionWrapper singleton bypass: the record is
+            // served as-is with its own RowKind
+            for (int c = 0; c < n_cols; c++) {
+                if (c == kind_col)
+                    ((int8_t *)out_ptrs[c])[i] = (int8_t)pac_kind(kinds, 0);
+                else
+                    pac_put_src(a, sink, c, 0);
+            }
+            continue;
+        }
+        bool has_add;
+        int last;
+        pac_row_summary(gn, kinds, ignore_delete, &has_add, &last);
+        ((int8_t *)out_ptrs[kind_col])[i] = has_add ? 0 : 3;
+        ((int64_t *)out_ptrs[seq_col])[i] =
+            last >= 0 ? a.load(last, seq_col) : 0;
+        bad |= pac_fold_row(a, gn, kinds, ignore_delete, tables, sink);
+    }
+    if (bad && err_flag) atomicOr(err_flag, PMH_ERR_PU_AGG_RETRACT);
 }
 
 // ------------------------------------------------------------ k_emit_agg
@@ -5201,9 +5336,13 @@ hipError_t pmh_launch_merge_tiles(const RunSet &runs, const TileSet &tiles,
     return hipGetLastError();
 }
 
+static int g_last_pu_emit_kernel = PMH_PU_EMIT_NONE;
+int pmh_last_pu_emit_kernel() { return g_last_pu_emit_kernel; }
+
 hipError_t pmh_launch_emit_pu(const RunSet &runs, const ColumnSet &columns,
                               const TileSet &tiles, int flags,
                               const OutputSet &out, hipStream_t stream) {
+    g_last_pu_emit_kernel = PMH_PU_EMIT_OVERLAY;
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(emit_grid()), dim3(256), 0, stream,
                            runs.cols, columns.dtype, columns.nullable,
@@ -5239,6 +5378,20 @@ hipError_t pmh_launch_emit_pu_sg(const RunSet &runs, const ColumnSet &columns,
                                  const SeqGroupSet &groups,
                                  const TileSet &tiles, int flags,
                                  const OutputSet &out, hipStream_t stream) {
+    if (groups.col_agg) {
+        g_last_pu_emit_kernel = PMH_PU_EMIT_SGA;
+        hipLaunchKernelGGL(k_emit_pu_sga, dim3(emit_grid()), dim3(256), 0,
+                           stream, runs.cols, columns.dtype, columns.nullable,
+                           columns.n_cols, runs.k, columns.seq_col(),
+                           columns.kind_col(), flags, groups.col_group,
+                           groups.fields, groups.nseq, groups.n_groups,
+                           groups.grp_cols, groups.grp_off, groups.col_agg,
+                           tiles.winners, tiles.group_start, tiles.offsets,
+                           tiles.n_tiles, PMH_TILE_ROWS, tiles.total,
+                           runs.masks, out.ptrs, out.valid, tiles.err);
+        return hipGetLastError();
+    }
+    g_last_pu_emit_kernel = PMH_PU_EMIT_SG;
     hipLaunchKernelGGL(k_emit_pu_sg, dim3(emit_grid()), dim3(256), 0, stream,
                        runs.cols, columns.dtype, columns.nullable,
                        columns.n_cols, runs.k, columns.seq_col(),

@@ -35,6 +35,7 @@
 #include "parquet_meta.h"
 #include "parquet_write.h"
 #include "partition_core.h"
+#include "pu_agg_core.h"
 
 #include <dlfcn.h>
 
@@ -707,6 +708,9 @@ struct pmh_plan_t {
     bool seqg = false;
     bool agg_retract = false;  // every aggregator retract-capable
     pmh::SeqGroupSet seq_groups;
+    // partial-update aggregate functions: [n_cols] PMH_AGG_* code
+    // (| PMH_AGG_IGNORE_RETRACT) or PAC_NONE; empty without any
+    std::vector<uint8_t> pu_col_agg;
     // changelog-producer = full-compaction (FullChangelogMergeFunction-
     // Wrapper): a second output stream of changelog rows per read_next
     bool changelog = false;
@@ -3030,6 +3034,33 @@ static int profile_flags() {
            field("PMH_FSTAGE", PMH_FLAG_FSTAGE_SHIFT, PMH_FLAG_FSTAGE_MASK);
 }
 
+// aggregate function names <-> PMH_AGG_* codes
+static int agg_code_of(const std::string &s) {
+    if (s == "last_non_null_value") return PMH_AGG_LAST_NON_NULL;
+    if (s == "last_value") return PMH_AGG_LAST_VALUE;
+    if (s == "first_value") return PMH_AGG_FIRST_VALUE;
+    if (s == "first_non_null_value" || s == "first_not_null_value")
+        return PMH_AGG_FIRST_NON_NULL;
+    if (s == "sum") return PMH_AGG_SUM;
+    if (s == "max") return PMH_AGG_MAX;
+    if (s == "min") return PMH_AGG_MIN;
+    if (s == "primary_key") return PMH_AGG_PRIMARY_KEY;
+    return -1;
+}
+
+static const char *agg_name_of(int code) {
+    switch (code & 0x7f) {
+    case PMH_AGG_LAST_NON_NULL: return "last_non_null_value";
+    case PMH_AGG_LAST_VALUE: return "last_value";
+    case PMH_AGG_FIRST_VALUE: return "first_value";
+    case PMH_AGG_FIRST_NON_NULL: return "first_non_null_value";
+    case PMH_AGG_SUM: return "sum";
+    case PMH_AGG_MAX: return "max";
+    case PMH_AGG_MIN: return "min";
+    default: return "primary_key";
+    }
+}
+
 // What a set device error word refuses the read with; empty for a clean one.
 static std::string error_word_message(const pmh_plan_t *p, uint32_t w) {
     if (w & PMH_ERR_RETRACT) {
@@ -3043,6 +3074,27 @@ static std::string error_word_message(const pmh_plan_t *p, uint32_t w) {
                "PartialUpdateMergeFunction.java:170-186); configure "
                "'partial-update.remove-record-on-delete', or wait "
                "for the sequence-group/retract-aggregator rounds";
+    }
+    if (w & PMH_ERR_PU_AGG_RETRACT) {
+        // FieldAggregator.retract throws; the candidates are the plan's
+        // group fields whose function has no retract and no ignore-retract
+        std::string cols;
+        for (size_t c = 0; c < p->pu_col_agg.size(); c++) {
+            const uint8_t a = p->pu_col_agg[c];
+            if (a == PAC_NONE || (a & PMH_AGG_IGNORE_RETRACT)) continue;
+            if (a != PMH_AGG_MAX && a != PMH_AGG_MIN &&
+                a != PMH_AGG_FIRST_VALUE && a != PMH_AGG_FIRST_NON_NULL)
+                continue;
+            cols += std::string(cols.empty() ? "" : ", ") + "'" +
+                    agg_name_of(a) + "' on column '" + p->cols[c].name + "'";
+        }
+        return "partial-update: a retract record (UPDATE_BEFORE / DELETE) "
+               "with a non-empty sequence group reached an aggregate "
+               "function that does not support retraction (" + cols +
+               "); list the column in ignore_retract "
+               "('fields.<field>.ignore-retract' = 'true') to let the "
+               "function ignore retraction messages "
+               "(FieldAggregator.retract)";
     }
     if (w & PMH_ERR_FIRST_ROW_RETRACT)
         return "first-row merge engine cannot accept DELETE/UPDATE_BEFORE "
@@ -3449,6 +3501,141 @@ pmh_session_t *pmh_open_session(int device) {
 
 void pmh_close_session(pmh_session_t *s) { delete s; }
 
+// The per-column aggregator table of both folding engines, from the plan's
+// "aggregations": {"col": "sum", ...} and "ignore_retract": ["col", ...]
+// ("first_not_null_value" is the legacy alias,
+// FieldFirstNonNullValueAggLegacyFactory.java:29). ca arrives filled with
+// each column's default and leaves with one PMH_AGG_* code per column
+// (| PMH_AGG_IGNORE_RETRACT).
+//
+// Aggregation engine (pu = false): unnamed value columns keep the
+// last_non_null_value they arrive with (AggregateMergeFunction.java:197-203).
+//
+// Partial-update (pu = true; getAggFuncName, PartialUpdateMergeFunction
+// .java:698-728): ca arrives PAC_NONE everywhere. "default_aggregation"
+// (fields.default-aggregate-function) fills every value column that is
+// neither a sequence field nor named; an entry that names a sequence field
+// gives it no aggregator; every function but last_non_null_value needs the
+// column to be a group_fields member of a sequence group (col_group /
+// is_seq_field: the plan's sequence-group tables, empty without groups).
+static bool parse_agg_table(pmh_plan_t *plan, const Json &j, bool pu,
+                            const std::vector<uint8_t> &col_group,
+                            const std::vector<uint8_t> &is_seq_field,
+                            std::vector<uint8_t> &ca) {
+    const int n_cols = (int)plan->cols.size();
+    const int first_val = plan->columns.first_val();
+    // one function on one column: the type rules, and under partial-update
+    // the sequence-group rule
+    auto check = [&](int idx, const std::string &fn, int code) -> bool {
+        if (code < 0) {
+            set_error("aggregate function '%s' not on the GPU path "
+                      "(v1: sum, max, min, last_value, first_value, "
+                      "last_non_null_value, first_non_null_value)",
+                      fn.c_str());
+            return false;
+        }
+        if (pu && code == PMH_AGG_PRIMARY_KEY) {
+            set_error("aggregate function 'primary_key' on column '%s': "
+                      "partial-update keys are key columns, not value "
+                      "columns, and take no aggregate function",
+                      plan->cols[idx].name.c_str());
+            return false;
+        }
+        if (plan->cols[idx].dtype == PMH_DT_STRING &&
+            (code == PMH_AGG_SUM || code == PMH_AGG_MAX ||
+             code == PMH_AGG_MIN)) {
+            set_error("aggregate '%s' on a string column is not on "
+                      "the GPU path (ids are not ordered by value)",
+                      fn.c_str());
+            return false;
+        }
+        if ((plan->cols[idx].is_bool || plan->cols[idx].logical) &&
+            code == PMH_AGG_SUM) {
+            set_error("aggregate 'sum' on %s column '%s' is not "
+                      "supported (boolean / date / time / timestamp "
+                      "columns take last_value, first_value, "
+                      "last_non_null_value, first_non_null_value, "
+                      "max, min)",
+                      plan->cols[idx].is_bool
+                          ? "boolean"
+                          : logical_name(plan->cols[idx].logical),
+                      plan->cols[idx].name.c_str());
+            return false;
+        }
+        if (!pu && plan->rrod && (code == PMH_AGG_FIRST_VALUE ||
+                                  code == PMH_AGG_FIRST_NON_NULL)) {
+            set_error("aggregate function '%s' is not supported "
+                      "with remove-record-on-delete in v1 (its "
+                      "initialized-state does not reset on DELETE "
+                      "in the reference; later round)",
+                      fn.c_str());
+            return false;
+        }
+        if (pu && code != PMH_AGG_LAST_NON_NULL &&
+            (col_group.empty() || col_group[idx] == 0xff)) {
+            set_error("Must use sequence group for aggregation functions "
+                      "but not found for field %s.",
+                      plan->cols[idx].name.c_str());
+            return false;
+        }
+        return true;
+    };
+    auto seq_field = [&](int c) {
+        return !is_seq_field.empty() && is_seq_field[c];
+    };
+    std::vector<uint8_t> named(n_cols, 0);
+    for (const auto &kv : j["aggregations"].obj) {
+        int idx = -1;
+        for (int c = first_val; c < n_cols; c++)
+            if (plan->cols[c].name == kv.first) idx = c;
+        if (idx < 0) {
+            set_error("aggregations: '%s' is not a value column",
+                      kv.first.c_str());
+            return false;
+        }
+        named[idx] = 1;
+        // no aggregate function for sequence fields (getAggFuncName)
+        if (pu && seq_field(idx)) continue;
+        const std::string fn = kv.second.as_str();
+        const int code = agg_code_of(fn);
+        if (!check(idx, fn, code)) return false;
+        ca[idx] = (uint8_t)code;
+    }
+    if (pu) {
+        const std::string dfl = j["default_aggregation"].as_str("");
+        if (!dfl.empty()) {
+            const int code = agg_code_of(dfl);
+            for (int c = first_val; c < n_cols; c++) {
+                if (named[c] || seq_field(c)) continue;
+                if (!check(c, dfl, code)) return false;
+                ca[c] = (uint8_t)code;
+            }
+        }
+    }
+    // fields.<f>.ignore-retract = true (FieldIgnoreRetractAgg):
+    // retract records leave that field's accumulator untouched
+    for (const auto &irj : j["ignore_retract"].arr) {
+        int idx = -1;
+        for (int c = first_val; c < n_cols; c++)
+            if (plan->cols[c].name == irj.as_str()) idx = c;
+        if (idx < 0) {
+            set_error("ignore_retract: '%s' is not a value column",
+                      irj.as_str().c_str());
+            return false;
+        }
+        if (pu && ca[idx] == PAC_NONE) {
+            // stricter than the reference, which drops the option silently
+            set_error("ignore_retract: column '%s' has no aggregate "
+                      "function under partial-update (name one in "
+                      "aggregations or default_aggregation)",
+                      irj.as_str().c_str());
+            return false;
+        }
+        ca[idx] |= PMH_AGG_IGNORE_RETRACT;
+    }
+    return true;
+}
+
 pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
     if (!s) {
         set_error("null session");
@@ -3561,6 +3748,8 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                               // by default, :170-186)
             plan->rrod = j["remove_record_on_delete"].as_bool(false);
             const Json &sgs = j["sequence_groups"];
+            // host copies for the aggregator table below
+            std::vector<uint8_t> sg_col_group, sg_is_seq_field;
             if (!sgs.arr.empty()) {
                 plan->seqg = true;
                 if (sgs.arr.size() > 16) {
@@ -3632,6 +3821,58 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
                 }
                 plan->seq_groups =
                     SeqGroupSet{cg_dev, sf_dev, ns_dev, (int)sgs.arr.size()};
+                sg_col_group = cg;
+                sg_is_seq_field.assign(n_cols, 0);
+                for (int16_t c : sf)
+                    if (c >= 0) sg_is_seq_field[c] = 1;
+            }
+            {
+                // fields.<f>.aggregate-function inside sequence groups: a
+                // group field with an aggregator sends the plan's emit to
+                // k_emit_pu_sga. last_non_null_value on a field in no group
+                // equals the overlay and needs nothing.
+                const int n_cols = (int)plan->cols.size();
+                std::vector<uint8_t> ca(n_cols, PAC_NONE);
+                if (!parse_agg_table(plan.get(), j, true, sg_col_group,
+                                     sg_is_seq_field, ca))
+                    return nullptr;
+                bool any = false;
+                for (int c = 0; c < n_cols; c++)
+                    any |= ca[c] != PAC_NONE && !sg_col_group.empty() &&
+                           sg_col_group[c] != 0xff;
+                if (any) {
+                    // per-group column lists: a group's fields that are no
+                    // sequence fields, next to col_group
+                    const int ng = plan->seq_groups.n_groups;
+                    std::vector<int16_t> gc;
+                    std::vector<uint16_t> go(ng + 1, 0);
+                    for (int g = 0; g < ng; g++) {
+                        for (int c = 0; c < n_cols; c++)
+                            if (sg_col_group[c] == g && !sg_is_seq_field[c])
+                                gc.push_back((int16_t)c);
+                        go[g + 1] = (uint16_t)gc.size();
+                    }
+                    int16_t *gc_dev = (int16_t *)plan->bufs.alloc(
+                        std::max<size_t>(gc.size(), 1) * 2);
+                    uint16_t *go_dev =
+                        (uint16_t *)plan->bufs.alloc(go.size() * 2);
+                    uint8_t *ca_dev = (uint8_t *)plan->bufs.alloc(n_cols);
+                    if (!gc_dev || !go_dev || !ca_dev ||
+                        hipMemcpy(gc_dev, gc.data(), gc.size() * 2,
+                                  hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(go_dev, go.data(), go.size() * 2,
+                                  hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(ca_dev, ca.data(), n_cols,
+                                  hipMemcpyHostToDevice) != hipSuccess) {
+                        set_error("H2D of partial-update aggregator tables "
+                                  "failed");
+                        return nullptr;
+                    }
+                    plan->seq_groups.grp_cols = gc_dev;
+                    plan->seq_groups.grp_off = go_dev;
+                    plan->seq_groups.col_agg = ca_dev;
+                    plan->pu_col_agg = ca;
+                }
             }
         } else if (engine == "first-row") {
             plan->first_row = true;  // FirstRowMergeFunction.java:32-77
@@ -4156,87 +4397,12 @@ pmh_plan_t *pmh_plan_create(pmh_session_t *s, const char *plan_json) {
         }
         for (auto &cs : plan->cols) plan->col_names.push_back(cs.name);
         if (plan->agg) {
-            // "aggregations": {"col": "sum", ...}; unnamed value columns get
-            // last_non_null_value (AggregateMergeFunction.java:197-203);
-            // "first_not_null_value" is the legacy alias
-            // (FieldFirstNonNullValueAggLegacyFactory.java:29)
+            // unnamed value columns get last_non_null_value
+            // (AggregateMergeFunction.java:197-203)
             std::vector<uint8_t> ca(n_cols, PMH_AGG_LAST_NON_NULL);
-            auto code_of = [](const std::string &s) -> int {
-                if (s == "last_non_null_value") return PMH_AGG_LAST_NON_NULL;
-                if (s == "last_value") return PMH_AGG_LAST_VALUE;
-                if (s == "first_value") return PMH_AGG_FIRST_VALUE;
-                if (s == "first_non_null_value" ||
-                    s == "first_not_null_value")
-                    return PMH_AGG_FIRST_NON_NULL;
-                if (s == "sum") return PMH_AGG_SUM;
-                if (s == "max") return PMH_AGG_MAX;
-                if (s == "min") return PMH_AGG_MIN;
-                if (s == "primary_key") return PMH_AGG_PRIMARY_KEY;
-                return -1;
-            };
             const int first_val = plan->columns.first_val();
-            for (const auto &kv : j["aggregations"].obj) {
-                int idx = -1;
-                for (int c = first_val; c < n_cols; c++)
-                    if (plan->cols[c].name == kv.first) idx = c;
-                if (idx < 0) {
-                    set_error("aggregations: '%s' is not a value column",
-                              kv.first.c_str());
-                    return nullptr;
-                }
-                int code = code_of(kv.second.as_str());
-                if (code < 0) {
-                    set_error("aggregate function '%s' not on the GPU path "
-                              "(v1: sum, max, min, last_value, first_value, "
-                              "last_non_null_value, first_non_null_value)",
-                              kv.second.as_str().c_str());
-                    return nullptr;
-                }
-                if (plan->cols[idx].dtype == PMH_DT_STRING &&
-                    (code == PMH_AGG_SUM || code == PMH_AGG_MAX ||
-                     code == PMH_AGG_MIN)) {
-                    set_error("aggregate '%s' on a string column is not on "
-                              "the GPU path (ids are not ordered by value)",
-                              kv.second.as_str().c_str());
-                    return nullptr;
-                }
-                if ((plan->cols[idx].is_bool || plan->cols[idx].logical) &&
-                    code == PMH_AGG_SUM) {
-                    set_error("aggregate 'sum' on %s column '%s' is not "
-                              "supported (boolean / date / time / timestamp "
-                              "columns take last_value, first_value, "
-                              "last_non_null_value, first_non_null_value, "
-                              "max, min)",
-                              plan->cols[idx].is_bool
-                                  ? "boolean"
-                                  : logical_name(plan->cols[idx].logical),
-                              kv.first.c_str());
-                    return nullptr;
-                }
-                if (plan->rrod && (code == PMH_AGG_FIRST_VALUE ||
-                                   code == PMH_AGG_FIRST_NON_NULL)) {
-                    set_error("aggregate function '%s' is not supported "
-                              "with remove-record-on-delete in v1 (its "
-                              "initialized-state does not reset on DELETE "
-                              "in the reference; later round)",
-                              kv.second.as_str().c_str());
-                    return nullptr;
-                }
-                ca[idx] = (uint8_t)code;
-            }
-            // fields.<f>.ignore-retract = true (FieldIgnoreRetractAgg):
-            // retract records leave that field's accumulator untouched
-            for (const auto &irj : j["ignore_retract"].arr) {
-                int idx = -1;
-                for (int c = first_val; c < n_cols; c++)
-                    if (plan->cols[c].name == irj.as_str()) idx = c;
-                if (idx < 0) {
-                    set_error("ignore_retract: '%s' is not a value column",
-                              irj.as_str().c_str());
-                    return nullptr;
-                }
-                ca[idx] |= PMH_AGG_IGNORE_RETRACT;
-            }
+            if (!parse_agg_table(plan.get(), j, false, {}, {}, ca))
+                return nullptr;
             // retract records are accepted iff EVERY value column's
             // aggregator supports retraction (FieldSumAgg.retract,
             // FieldPrimaryKeyAgg) or ignores it (ignore-retract wrapper) —
@@ -5187,6 +5353,35 @@ int pmh_debug_changelog_decide(int64_t n_groups, const int32_t *nlive,
 }
 
 int pmh_debug_last_emit_kernel(void) { return pmh_last_emit_kernel(); }
+int pmh_debug_last_pu_emit_kernel(void) { return pmh_last_pu_emit_kernel(); }
+
+// CPU-side entry to the partial-update aggregate fold (pu_agg_core.h): one
+// key group through the code k_emit_pu_sga runs per output row.
+int pmh_debug_pu_agg_fold(int n_members, const int8_t *kinds, int n_cols,
+                          const uint8_t *dtypes, const int64_t *values,
+                          const uint8_t *valid, int n_groups,
+                          const uint8_t *col_group, const int16_t *sg_fields,
+                          const uint8_t *sg_nseq, const uint8_t *col_agg,
+                          int ignore_delete, int64_t *out_values,
+                          uint8_t *out_valid, int32_t *out_kind,
+                          int32_t *out_last, int32_t *out_unsupported) {
+    if (!kinds || !dtypes || !values || !valid || !col_group || !col_agg ||
+        (n_groups > 0 && (!sg_fields || !sg_nseq)) || !out_values ||
+        !out_valid || !out_kind || !out_last || !out_unsupported) {
+        set_error("pmh_debug_pu_agg_fold: null argument");
+        return -1;
+    }
+    const char *what = pac_host_check(n_members, n_cols, n_groups, col_group,
+                                      sg_fields, sg_nseq);
+    if (what) {
+        set_error("pmh_debug_pu_agg_fold: %s", what);
+        return -1;
+    }
+    pac_host_fold(n_members, kinds, n_cols, dtypes, values, valid, n_groups,
+                  col_group, sg_fields, sg_nseq, col_agg, ignore_delete != 0,
+                  out_values, out_valid, out_kind, out_last, out_unsupported);
+    return 0;
+}
 
 int pmh_debug_partition(int k, const void *const *keys, const int64_t *lens,
                         int key_width, int64_t tile_rows, int mode,

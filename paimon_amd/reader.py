@@ -556,6 +556,74 @@ def debug_last_emit_kernel():
     return int(lib.pmh_debug_last_emit_kernel())
 
 
+PU_EMIT_NONE, PU_EMIT_OVERLAY, PU_EMIT_SG, PU_EMIT_SGA = 0, 1, 2, 3
+
+
+def debug_last_pu_emit_kernel():
+    """The partial-update emit kernel the last read of this process
+    launched: PU_EMIT_OVERLAY (k_emit_pu), PU_EMIT_SG (k_emit_pu_sg),
+    PU_EMIT_SGA (k_emit_pu_sga, aggregate functions inside sequence groups),
+    or PU_EMIT_NONE before the first one."""
+    lib = load_lib()
+    lib.pmh_debug_last_pu_emit_kernel.restype = ctypes.c_int
+    lib.pmh_debug_last_pu_emit_kernel.argtypes = []
+    return int(lib.pmh_debug_last_pu_emit_kernel())
+
+
+PU_AGG_CODES = {"last_non_null_value": 0, "last_value": 1, "first_value": 2,
+                "first_non_null_value": 3, "sum": 4, "max": 5, "min": 6}
+PU_AGG_IGNORE_RETRACT = 0x80
+PU_AGG_NONE = 0xff
+
+
+def debug_pu_agg_fold(kinds, dtypes, values, valid, col_group, sg_fields,
+                      sg_nseq, col_agg, ignore_delete=False):
+    """One key group through the partial-update aggregate fold on the host
+    (pmh_debug_pu_agg_fold; the core k_emit_pu_sga runs). kinds [n] RowKind
+    bytes in merge order; values / valid [n, n_cols] (values as int64 bits);
+    dtypes, col_group, col_agg [n_cols]; sg_fields [n_groups, 4]; sg_nseq
+    [n_groups]. Returns (values [n_cols] int64, valid [n_cols] bool, kind,
+    last member index or -1, unsupported-retraction flag)."""
+    lib = load_lib()
+    kinds = np.ascontiguousarray(kinds, np.int8)
+    dtypes = np.ascontiguousarray(dtypes, np.uint8)
+    values = np.ascontiguousarray(values, np.int64)
+    valid = np.ascontiguousarray(valid, np.uint8)
+    col_group = np.ascontiguousarray(col_group, np.uint8)
+    sg_fields = np.ascontiguousarray(sg_fields, np.int16).reshape(-1)
+    sg_nseq = np.ascontiguousarray(sg_nseq, np.uint8)
+    col_agg = np.ascontiguousarray(col_agg, np.uint8)
+    n, n_cols = len(kinds), len(dtypes)
+    assert values.shape == (n, n_cols) and valid.shape == (n, n_cols)
+    assert len(col_group) == n_cols and len(col_agg) == n_cols
+    assert len(sg_fields) == 4 * len(sg_nseq)
+    out_v = np.zeros(n_cols, np.int64)
+    out_ok = np.zeros(n_cols, np.uint8)
+    kind = ctypes.c_int32(0)
+    last = ctypes.c_int32(0)
+    unsup = ctypes.c_int32(0)
+    fn = lib.pmh_debug_pu_agg_fold
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                   ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.POINTER(ctypes.c_int32),
+                   ctypes.POINTER(ctypes.c_int32),
+                   ctypes.POINTER(ctypes.c_int32)]
+    rc = fn(n, kinds.ctypes.data, n_cols, dtypes.ctypes.data,
+            values.ctypes.data, valid.ctypes.data, len(sg_nseq),
+            col_group.ctypes.data, sg_fields.ctypes.data or None,
+            sg_nseq.ctypes.data or None, col_agg.ctypes.data,
+            int(bool(ignore_delete)), out_v.ctypes.data, out_ok.ctypes.data,
+            ctypes.byref(kind), ctypes.byref(last), ctypes.byref(unsup))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out_v, out_ok.astype(bool), kind.value, last.value, \
+        bool(unsup.value)
+
+
 class Session:
     def __init__(self, device=0):
         self.lib = load_lib()
@@ -586,7 +654,7 @@ class MergeReadPlan:
                  ignore_retract=None, sequence_fields=None,
                  changelog_producer=None, changelog_row_dedup=False,
                  max_level=None, sort_engine="loser-tree", filters=None,
-                 lookup_files=None):
+                 lookup_files=None, default_aggregation=None):
         self.lib = session.lib
         desc = {
             "key_cols": key_cols,
@@ -612,8 +680,15 @@ class MergeReadPlan:
             desc["sequence_fields"] = list(sequence_fields)
         if aggregations:
             # fields.<name>.aggregate-function (CoreOptions FIELDS_PREFIX);
-            # unnamed columns default to last_non_null_value
+            # aggregation: unnamed columns default to last_non_null_value;
+            # partial-update: the named columns are fields of a sequence
+            # group (last_non_null_value alone needs none)
             desc["aggregations"] = dict(aggregations)
+        if default_aggregation:
+            # fields.default-aggregate-function (partial-update): every
+            # value column that is neither a sequence field nor named in
+            # aggregations
+            desc["default_aggregation"] = str(default_aggregation)
         if filters:
             # value-filter conjunction; pushed into SINGLE-RUN sections
             # only (MergeFileSplitRead.java:227-239) — overlapping
